@@ -1,6 +1,14 @@
 """Benchmark: Mpixels/s of the render path (BASELINE.json metric) on 1..N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2] [--mode frames|tiles]
+    python bench.py --gpus N --steps K --warmup W [--config C2] [--mode frames|tiles] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, ramps the clock, warms up, times the K steps and prints the headline line
+(metric, value, unit, ms_per_step, ...). ``--full`` adds every other measurement to the line: the
+roofline (a counter launch of its own), the output path, the tiles-mode legs (``secondary``,
+``strong_scaling``) and the CPU baselines. ``--dump-outputs DIR`` writes what the last timed step
+returned to ``DIR/color.npy`` (float32, or float64 with ``--out f64``; a fixed seeded sample of an
+output over 64 MB, its indices in ``DIR/color_index.npy``).
 
 A *step* is one frame of the configuration through the public API — ``HipRenderer.raytrace_scene(
 camera.position, get_ray_directions(camera), scene)``: scene packing (cached by content), primary
@@ -12,17 +20,18 @@ Default workload: BASELINE.json configs[1] — the README scene at 1920x1080, 3 
 collective in the loop (the frame sharding of config C5), so N=1 and N>1 lines measure
 the same code path and output format. Rank r renders frame r of a camera path through the config's
 camera (``scenes.rank_frame_spec``): rank 0 the config's own frame, so the N = 1 line is unchanged,
-and N ranks render N distinct frames per step. The top-level ``strong_scaling`` object is the
+and N ranks render N distinct frames per step. The top-level ``strong_scaling`` object (``--full``) is the
 row-tiled C4 frame (below) with its measured speed-up over one GPU and its gather per link. ``--mode tiles`` (strong scaling): every rank renders its
 interleaved row tile of ONE frame and the uint8 tiles are gathered to rank 0 (RCCL) every step; the
-default line carries it at every N as ``secondary.tiles_u8`` (the config) and ``secondary.c4_tiles``
+``--full`` line carries it at every N as ``secondary.tiles_u8`` (the config) and ``secondary.c4_tiles``
 (C4, 7680x4320), on a one-rank process group at N=1.
 
 Timing: W untimed warm-up steps, then K steps bracketed by barrier + synchronize, max over ranks.
 The dominant kernel's own time is measured live with HIP events recorded by the library on the
 launch stream (rtx_profile_*) around one launch in --prof-every of the timed region, for the
-roofline (timing a launch costs stream time, so timing every launch would depress `value`). Rank 0 also times the CPU oracle (NumPy float64,
-single core) on a bounded sample of the same workload.
+roofline (timing a launch costs stream time, so timing every launch would depress `value`; a plain
+run samples the same launches, so `value` means the same with and without --full). With --full
+rank 0 also times the CPU oracle (NumPy float64, single core) on a bounded sample of the same workload.
 """
 
 from __future__ import annotations
@@ -51,6 +60,14 @@ def parse():
                     help="untimed steps for this long before the warm-up steps: the GPU leaves its idle clock "
                          "state (C2: 63.6 us kernel after 20 warm-up steps, 59.0 us from ~500 on, "
                          "profiles/r3_ramp.json); the timed region is still exactly --steps steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline (a counter launch), the "
+                         "output path, the tiles-mode legs of the config and of C4 (secondary, strong_scaling) "
+                         "and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to DIR/color.npy "
+                         "(float32, or float64 with --out f64; at most 64 MB: a fixed seeded sample of a larger "
+                         "output, its flat indices in DIR/color_index.npy)")
     ap.add_argument("--config", default="C2", help="C1|C2|C2main|C3|C4|C5 (python_ray_tracer_amd/scenes.py)")
     ap.add_argument("--mode", default="frames", choices=["frames", "tiles"],
                     help="frames (default: every rank renders whole frames, weak scaling) or tiles (row tiles + "
@@ -60,7 +77,7 @@ def parse():
                     help="frame format left in HBM (default f32; u8 in tiles mode: the gathered frame is the "
                          "uint8 image save_image writes)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the tiles-mode (row tiles + gather) measurements of the config and of C4")
+                    help="--full: skip the tiles-mode (row tiles + gather) measurements of the config and of C4")
     ap.add_argument("--cpu-procs", type=int, default=14,
                     help="processes of the row-tiled all-cores CPU baseline (the box's CPU share is 16 cores, and "
                          "at most 16 processes may hold the GPU open: importing torch opens it in every worker, "
@@ -70,7 +87,7 @@ def parse():
                          "SURVEY.md 8d) per step in ONE launch (rtx_render_frames)")
     ap.add_argument("--bounces", type=int, default=None,
                     help="override the config's bounce cap (-1: unbounded, HipRenderer()'s default)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline time budget (0: skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU-baseline time budget (0: skip)")
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--prof-every", type=int, default=10,
                     help="time the dominant kernel with HIP events on one launch in this many (timing a launch "
@@ -213,10 +230,11 @@ def main():
     every = max(1, min(args.prof_every, args.steps))
     L.profile_sample(every)
     L.profile_enable(args.steps)
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
-    drain()
+        last = step()
+    last_drained = drain()
     barrier()
     elapsed = time.perf_counter() - t0
     kern_ms, kern_n = L.profile_collect()
@@ -226,6 +244,51 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        if last_drained is not None:  # a gathering tiles plan: the root's last frame comes out of the drain
+            last = last_drained
+        dump_outputs(args.dump_outputs, last, rank)
+
+    ms_per_step = elapsed / args.steps * 1e3
+    value = px_per_step * args.steps / elapsed / 1e6
+    line = {
+        "metric": "Mpixels/sec @1920x1080, 3 reflection bounces" if args.config in ("C2", "C2main") and B == 3
+        else f"Mpixels/sec ({args.config}, {'unbounded' if B is None else B} bounces)",
+        "value": round(value, 3),
+        "unit": "Mpixels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ramp": {"ms": args.ramp_ms, "steps": n_ramp,
+                 "note": "untimed steps before the warm-up steps, bringing the GPU out of its idle clock "
+                         "state (profiles/r3_ramp.json)"},
+        "ms_per_step": round(ms_per_step, 5),
+        "higher_is_better": True,
+        "scaling": "weak" if args.mode == "frames" else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "output_dtype": {"f32": "f32 SoA", "f64": "f64 SoA", "u8": "u8 HWC"}[args.out],
+        "data": "synthetic",
+        "config": {"workload": f"{args.config}: " + WORKLOADS[args.config]
+                   + (", unbounded bounces" if B is None else f", {B} bounces"),
+                   "width": W, "height": H, "max_bounces": B, "spheres": len(spec["spheres"]), "output": args.out,
+                   "mode": args.mode, "frames_per_step": F, "parallelism": f"{args.mode}x{world}",
+                   "frames": ("one frame per rank and step: rank r renders frame r of the camera path through the "
+                              "config's camera (scenes.rank_frame_spec; rank 0 the config's frame)")
+                   if args.mode == "frames" and F == 1 else
+                   ("rank r renders orbit frames r*F .. r*F+F-1 of the 256-frame C5 orbit in one launch"
+                    if args.mode == "frames" else "one frame row-tiled over the ranks")},
+        "kernel_ms": round(kern_ms / max(kern_n, 1), 5),
+        "kernel_launches_timed": kern_n,
+    }
+    if not args.full:
+        if rank == 0:
+            emit(line, args.json_out)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # algorithmic work of one launch, from the kernel's own counters (checked against the oracle in
     # tests/test_gpu_parity.py): 15 flops / primary ray, 20 / ray-sphere test, 200 / shaded hit
@@ -287,41 +350,7 @@ def main():
         cpu = cpu_baseline_or_error(spec, B, args.cpu_procs, args.cpu_seconds, cpu)
 
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = px_per_step * args.steps / elapsed / 1e6
-        line = {
-            "metric": "Mpixels/sec @1920x1080, 3 reflection bounces" if args.config in ("C2", "C2main") and B == 3
-            else f"Mpixels/sec ({args.config}, {'unbounded' if B is None else B} bounces)",
-            "value": round(value, 3),
-            "unit": "Mpixels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ramp": {"ms": args.ramp_ms, "steps": n_ramp,
-                     "note": "untimed steps before the warm-up steps, bringing the GPU out of its idle clock "
-                             "state (profiles/r3_ramp.json)"},
-            "ms_per_step": round(ms_per_step, 5),
-            "higher_is_better": True,
-            "scaling": "weak" if args.mode == "frames" else "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "output_dtype": {"f32": "f32 SoA", "f64": "f64 SoA", "u8": "u8 HWC"}[args.out],
-            "data": "synthetic",
-            "config": {"workload": f"{args.config}: " + {
-                "C1": "README scene 960x540",
-                "C2": "README scene (BASELINE configs[1]) 1920x1080",
-                "C2main": "main.py scene 1920x1080",
-                "C3": "16 random spheres + checker ground 3840x2160 seed 0",
-                "C4": "64 random spheres + checker ground 7680x4320 seed 0",
-                "C5": "16 random spheres 1920x1080 seed 0"}[args.config]
-                + (", unbounded bounces" if B is None else f", {B} bounces"),
-                "width": W, "height": H, "max_bounces": B, "spheres": S, "output": args.out,
-                "mode": args.mode, "frames_per_step": F, "parallelism": f"{args.mode}x{world}",
-                "frames": ("one frame per rank and step: rank r renders frame r of the camera path through the "
-                           "config's camera (scenes.rank_frame_spec; rank 0 the config's frame)")
-                if args.mode == "frames" and F == 1 else
-                ("rank r renders orbit frames r*F .. r*F+F-1 of the 256-frame C5 orbit in one launch"
-                 if args.mode == "frames" else "one frame row-tiled over the ranks")},
+        line.update({
             "roofline": {
                 "bound": "valu",
                 "kernel": f"k_render_fast<{B}>" if B is not None and B <= 6 else "k_render_fast<5, DEEP> (first pass)",
@@ -370,7 +399,7 @@ def main():
             },
             "cpu_baseline": cpu,
             "output_path": out_path,
-        }
+        })
         if secondary:
             line["secondary"] = secondary
             ss = strong_scaling(secondary, world)
@@ -380,13 +409,55 @@ def main():
             line["gpu_vs_cpu"] = round(value / cpu["value"], 1)
             if cpu.get("single_core"):
                 line["gpu_vs_cpu_1core"] = round(value / cpu["single_core"]["value"], 1)
-        s = json.dumps(line)
-        print(s)
-        if args.json_out:
-            Path(args.json_out).write_text(s + "\n")
+        emit(line, args.json_out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+WORKLOADS = {
+    "C1": "README scene 960x540",
+    "C2": "README scene (BASELINE configs[1]) 1920x1080",
+    "C2main": "main.py scene 1920x1080",
+    "C3": "16 random spheres + checker ground 3840x2160 seed 0",
+    "C4": "64 random spheres + checker ground 7680x4320 seed 0",
+    "C5": "16 random spheres 1920x1080 seed 0"}
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def emit(line: dict, json_out) -> None:
+    """The one JSON result line on stdout (and in --json-out)."""
+    s = json.dumps(line)
+    print(s)
+    if json_out:
+        Path(json_out).write_text(s + "\n")
+
+
+def dump_outputs(folder, last, rank: int) -> None:
+    """--dump-outputs: the array the last timed step returned (the colour a caller of the timed path
+    receives), as ``color.npy`` (``color_rank<r>.npy`` on the other ranks of a frames-mode run; a
+    tiles-mode peer has no frame). float64 stays float64, everything else is written as float32. An
+    output over DUMP_MAX_BYTES is sampled at fixed flat indices (seed 0, sorted), kept beside it."""
+    import numpy as np
+    import torch
+
+    if last is None:
+        return
+    t = last if isinstance(last, torch.Tensor) else last.data
+    out_dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+    name = "color" if rank == 0 else f"color_rank{rank}"
+    folder = Path(folder)
+    folder.mkdir(parents=True, exist_ok=True)
+    # the index array (int64) counts against the limit too
+    keep = DUMP_MAX_BYTES // (out_dtype.itemsize + 8) - 64
+    if t.numel() * out_dtype.itemsize <= DUMP_MAX_BYTES - 256:
+        arr = t.to(out_dtype).cpu().numpy()
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=keep, replace=False))
+        arr = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].to(out_dtype).cpu().numpy()
+        np.save(folder / f"{name}_index.npy", idx)
+    np.save(folder / f"{name}.npy", arr)
 
 
 def frame_spec_for_rank(spec: dict, rank: int) -> dict:
@@ -430,10 +501,12 @@ def tiles_stepper(r, scene, world, row_block, out, loopback=False, comm_reserve=
     step.tg = tg
     step.timing = lambda: tg.timing(state["last"])
 
-    def drain():
+    def drain():  # the last frame (on the root), or None with nothing in flight
+        frame = None
         if state["open"] is not None:
-            tg.finish(state["open"])
+            frame = tg.finish(state["open"])
             state["open"] = None
+        return frame
     return step, drain
 
 

@@ -61,8 +61,8 @@ def _check(spec, Bs, dev):
 
 
 def test_bench_line_contract(tmp_path):
-    """bench.py at N = 1 prints ONE JSON line with the driver's contract fields, the roofline and
-    the top-level strong_scaling object (the row-tiled C4 frame on a one-rank loopback plan, its
+    """bench.py --full at N = 1 prints ONE JSON line with the driver's contract fields, the roofline
+    and the top-level strong_scaling object (the row-tiled C4 frame on a one-rank loopback plan, its
     gather labelled as HBM, not xGMI); a short run, CPU baseline skipped."""
     import json
     import subprocess
@@ -73,9 +73,9 @@ def test_bench_line_contract(tmp_path):
         pytest.skip("no GPU")
     repo = Path(__file__).resolve().parent.parent
     out = tmp_path / "line.json"
-    p = subprocess.run([sys.executable, str(repo / "bench.py"), "--steps", "5", "--warmup", "1", "--ramp-ms", "10",
-                        "--cpu-seconds", "0", "--json-out", str(out)], cwd=str(repo), capture_output=True, text=True,
-                       timeout=110)
+    p = subprocess.run([sys.executable, str(repo / "bench.py"), "--full", "--steps", "5", "--warmup", "1",
+                        "--ramp-ms", "10", "--cpu-seconds", "0", "--json-out", str(out)], cwd=str(repo),
+                       capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [s for s in p.stdout.splitlines() if s.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -95,3 +95,42 @@ def test_bench_line_contract(tmp_path):
     assert ss["n_gpus"] == 1 and ss["speedup_vs_1gpu"] > 0 and ss["single_gpu_ms_per_step"] > 0
     assert ss["gather"]["link"] == "loopback (HBM)" and ss["gather"]["xgmi_GBps_per_peer"] is None
     assert ss["xgmi_GBps"]["measured"] is None and ss["xgmi_GBps"]["assumed"] > 0
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints ONE JSON line with the headline fields and none of
+    the --full legs, times exactly --steps steps, and --dump-outputs writes the last timed frame:
+    float32 [3, W*H], bit-equal to the same public-API render in this process."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    dev = _dev()
+    repo = Path(__file__).resolve().parent.parent
+    p = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--ramp-ms", "10", "--config", "C1", "--dump-outputs", str(tmp_path / "dump")],
+                       cwd=str(repo), capture_output=True, text=True, timeout=110)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [s for s in p.stdout.splitlines() if s.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "secondary", "strong_scaling", "cpu_baseline", "output_path"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "Mpixels/s" and d["higher_is_better"] and d["dtype"] == "f64"
+    assert abs(d["value"] - 960 * 540 / d["ms_per_step"] / 1e3) <= 1e-3 * d["value"]
+    assert sorted(f.name for f in (tmp_path / "dump").iterdir()) == ["color.npy"]
+    got = np.load(tmp_path / "dump" / "color.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 960 * 540)
+
+    from python_ray_tracer_amd import scenes
+    from python_ray_tracer_amd.infrastructure.hip import HipRenderer
+
+    spec, B = scenes.CONFIGS["C1"]()
+    scene = scenes.build_scene(spec)
+    r = HipRenderer(max_bounces=B, color_dtype=torch.float32, device=dev)
+    want = r.raytrace_scene(scene.camera.position, r.get_ray_directions(scene.camera), scene).data.cpu().numpy()
+    assert np.array_equal(got, want)

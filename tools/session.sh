@@ -10,7 +10,7 @@
 #   tests            pytest -m gpu (one process, per-test time limit)
 #   tests:EXPR       pytest -m gpu -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (bench.py with no flags: what the driver runs)
+#   bench            the default bench line with every leg (bench.py --full)
 #   bench2[:C]       bench.py at N = 2 over gloo, both ranks on the one GPU (the N > 1 code path)
 #   unbounded:C      config C's line with the reference's unbounded recursion (HipRenderer's default)
 #   bench:C          bench line of config C (C1 C2 C2main C3 C4 C5), CPU baselines included
@@ -62,40 +62,40 @@ for step in "$@"; do
     smoke) run smoke 300 python __graft_entry__.py smoke ;;
     unbounded)
       # the drop-in default: HipRenderer() with the reference's unbounded recursion
-      run "unbounded_$arg" 300 python bench.py $(bargs "$arg") --bounces -1 --cpu-seconds 0 --no-secondary \
+      run "unbounded_$arg" 300 python bench.py --full $(bargs "$arg") --bounces -1 --cpu-seconds 0 --no-secondary \
         --json-out "$O/unbounded_$arg.json" ;;
     bench)
       if [ -n "$arg" ]; then
-        run "bench_$arg" 300 python bench.py $(bargs "$arg") --cpu-seconds 10 --json-out "$O/bench_$arg.json"
+        run "bench_$arg" 300 python bench.py --full $(bargs "$arg") --cpu-seconds 10 --json-out "$O/bench_$arg.json"
       else
-        run bench_default 300 python bench.py --json-out "$O/bench_default.json"
+        run bench_default 300 python bench.py --full --json-out "$O/bench_default.json"
       fi ;;
     bench2)
       # two ranks sharing the box's one GPU over gloo (bench.py --backend gloo): the N > 1 frames line
       # (distinct frames per rank), strong_scaling and the tiles legs through the gloo path
       run bench2_gloo 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus 2 --backend gloo --config "${arg:-C2}" --steps 50 --warmup 5 \
+        --master-port 29517 bench.py --full --gpus 2 --backend gloo --config "${arg:-C2}" --steps 50 --warmup 5 \
         --cpu-seconds 0 --json-out "$O/bench2_gloo.json" ;;
     rocprof)
       run "rocprof_$arg" 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$arg" -o run -- \
-        python3 bench.py $(bargs "$arg") --cpu-seconds 0 --no-secondary ;;
+        python3 bench.py --full $(bargs "$arg") --cpu-seconds 0 --no-secondary ;;
     pmc)
       P="--config $arg --steps 10 --warmup 2 --cpu-seconds 0 --no-secondary --ramp-ms 50"
       [ "$arg" = C5 ] && P="$P --frames-per-step 32"  # the C5 bench line's launch: 32 frames
       run "pmc_fetch_$arg" 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_$arg/fetch" -o run -- \
-        python3 bench.py $P
+        python3 bench.py --full $P
       run "pmc_write_$arg" 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/pmc_$arg/write" -o run -- \
-        python3 bench.py $P
+        python3 bench.py --full $P
       run "pmc_sq_$arg" 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES \
         SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d "$O/pmc_$arg/sq" -o run -- \
-        python3 bench.py $P
+        python3 bench.py --full $P
       run "pmc_valu_$arg" 120 rocprofv3 --pmc SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 \
         SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_THREAD_CYCLES_VALU --output-format csv \
-        -d "$O/pmc_$arg/valu" -o run -- python3 bench.py $P ;;
+        -d "$O/pmc_$arg/valu" -o run -- python3 bench.py --full $P ;;
     emul)
       run "emul_$arg" 300 python bench.py --config "$arg" --emulate-parts 2,4,8 --steps 20 --json-out "$O/emul_$arg.json" ;;
     tiles)
-      run "tiles_$arg" 300 python bench.py --config "$arg" --mode tiles --loopback --steps 20 --warmup 3 --cpu-seconds 0 \
+      run "tiles_$arg" 300 python bench.py --full --config "$arg" --mode tiles --loopback --steps 20 --warmup 3 --cpu-seconds 0 \
         --json-out "$O/tiles_$arg.json" ;;
     fuzz)
       n=${arg%%:*}
