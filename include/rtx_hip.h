@@ -18,6 +18,8 @@
  *   rtx_sphere_intersect<- NumpySphere.intersect             (shape.py:28-51)
  *   rtx_quantize_u8     <- NumpyRenderer.save_image's (255*clip(c,0,1)).astype(uint8)
  *                                                             (base.py:143-151)
+ *   rtx_resolve_samples <- no counterpart: the box filter of supersampled anti-aliasing
+ *                          (HipRenderer(samples=k)); each sample clipped as save_image clips a pixel
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -47,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RTX_ABI_VERSION 1
+#define RTX_ABI_VERSION 2 /* 2: rtx_resolve_samples */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -346,6 +348,26 @@ int rtx_sphere_intersect(const double* sphere, const double* origins, int64_t or
 /* save_image's quantisation (base.py:143-151): color [3][n] (RTX_OUT_F32_SOA or _F64_SOA) ->
  * out [n][3] uint8 = (uint8)(255 * clip(c, 0, 1)). */
 int rtx_quantize_u8(const void* color, int color_kind, int64_t n, uint8_t* out, void* stream);
+
+/* Supersampled anti-aliasing, the resolve (HipRenderer(samples=k); the reference renders one
+ * sample per pixel): the box filter of a frame rendered with k x k samples per pixel. The screen is
+ * fixed (base.py:130-141), so the render of the same scene and camera position at
+ * (k*width) x (k*height) holds exactly the k x k samples of every pixel.
+ * samples: n_frames x double [3][(k*n_rows) * (k*width)], each as an RTX_OUT_F64_SOA render of a
+ * (k*width)-wide frame with k*n_rows local rows wrote it. out: n_frames x (width x n_rows pixels
+ * as out_kind says). Per output pixel (r, c) and channel, in float64 and in exactly this order:
+ *   acc = 0.0; for sy in 0..k-1 (top to bottom): for sx in 0..k-1 (left to right):
+ *     acc = acc + clip(S[k*r + sy][k*c + sx], 0, 1)
+ *   value = acc / (double)(k*k)                       (one correctly rounded division)
+ * then RTX_OUT_F64_SOA stores value, RTX_OUT_F32_SOA value rounded once, RTX_OUT_U8_HWC
+ * (uint8)(255 * value) truncated. Each sample is clipped before it is averaged, as save_image
+ * would have clipped that pixel (one sample of 190 would otherwise whiten the whole pixel), so
+ * the colour outputs lie in [0, 1] (an unresolved render's colour is unclipped). A NaN sample
+ * counts as 0 where np.clip would keep it; no sample of a valid scene is NaN. k = 1 clips and
+ * converts. RTX_E_ARG (before any HIP call) for a null pointer, k outside 1..8, a non-positive
+ * size, an unknown out_kind, or k*k*width*n_rows*n_frames >= 2^31. */
+int rtx_resolve_samples(const double* samples, int k, int width, int n_rows, int n_frames,
+                        void* out, int out_kind, void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

@@ -11,6 +11,8 @@
 //   rt::quantize_u8   <- save_image's (255*clip(c,0,1)).astype(uint8) (base.py:143-151)
 //   rt::assemble_rows <- the multi-GPU frame's row un-permute (application.render_frame_distributed),
 //                        equal shares or weighted ones (root_run / run: rtx_assemble_runs)
+//   rt::resolve_samples <- no counterpart: the box filter of a k x k supersampled frame
+//                        (HipRenderer(samples=k), rtx_resolve_samples)
 //   rt::status        <- reads and clears the workspace's sticky RTX_ST_* flags
 //   rt::comm_unique_id, rt::comm_init, rt::comm_destroy, rt::tiles_create, rt::tiles_submit,
 //   rt::tiles_finish, rt::tiles_destroy
@@ -370,6 +372,39 @@ at::Tensor assemble_rows(const at::Tensor& tiles, int64_t width, int64_t height,
   return out;
 }
 
+// samples [3, k*rows*k*width] or [F, 3, ...] float64; returns the frame's shape and the frame count
+// (0: unbatched). Shared by the kernel and its Meta form.
+int64_t check_samples_shape(const at::Tensor& samples, int64_t k, int64_t width, int64_t rows, int64_t out_kind) {
+  TORCH_CHECK(k >= 1 && k <= 8, "k (samples per pixel side) must be in 1..8, got ", k);
+  TORCH_CHECK(width > 0 && rows > 0, "bad frame geometry (width ", width, ", rows ", rows, ")");
+  TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA || out_kind == RTX_OUT_U8_HWC,
+              "bad out_kind ", out_kind);
+  TORCH_CHECK(samples.scalar_type() == at::kDouble, "samples must be ", at::kDouble, ", got ", samples.scalar_type());
+  TORCH_CHECK((samples.dim() == 2 || samples.dim() == 3) && samples.size(-2) == 3,
+              "samples must be [3, k*rows*k*width] or [F, 3, k*rows*k*width]");
+  const int64_t frames = samples.dim() == 3 ? samples.size(0) : 0;
+  TORCH_CHECK(samples.dim() == 2 || frames >= 1, "samples holds no frame");
+  TORCH_CHECK(width <= INT32_MAX && rows <= INT32_MAX && frames <= INT32_MAX &&
+                  (double)(k * k) * (double)width * (double)rows * (double)(frames ? frames : 1) < 2147483648.0,
+              "k*k*width*rows*frames must stay below 2^31");
+  const int64_t ns = k * rows * k * width;
+  TORCH_CHECK(samples.size(-1) == ns, "samples holds ", samples.size(-1), " samples per plane, but k=", k, ", width=",
+              width, ", rows=", rows, " need ", ns, " (", (frames ? frames : 1) * 3 * ns, " in all, got ",
+              samples.numel(), ")");
+  return frames;
+}
+
+at::Tensor resolve_samples(const at::Tensor& samples, int64_t k, int64_t width, int64_t rows, int64_t out_kind) {
+  check_gpu(samples, "samples", at::kDouble);
+  const int64_t frames = check_samples_shape(samples, k, width, rows, out_kind);
+  const at::OptionalDeviceGuard guard(at::device_of(samples));
+  at::Tensor out = new_output(samples, rows * width, rows, width, out_kind, frames);
+  check_rc(rtx_resolve_samples(samples.data_ptr<double>(), (int)k, (int)width, (int)rows, (int)(frames ? frames : 1),
+                               out.data_ptr(), (int)out_kind, stream_of(samples)),
+           "rtx_resolve_samples");
+  return out;
+}
+
 int64_t status(at::Tensor& workspace) {
   check_gpu(workspace, "workspace", at::kByte);
   TORCH_CHECK(workspace.numel() >= RTX_WS_HDR_BYTES, "workspace shorter than its header");
@@ -524,6 +559,11 @@ at::Tensor assemble_rows_meta(const at::Tensor& tiles, int64_t width, int64_t he
   return assemble_out(tiles, width, height, out_kind);
 }
 
+at::Tensor resolve_samples_meta(const at::Tensor& samples, int64_t k, int64_t width, int64_t rows, int64_t out_kind) {
+  const int64_t frames = check_samples_shape(samples, k, width, rows, out_kind);
+  return new_output(samples, rows * width, rows, width, out_kind, frames);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rt, m) {
@@ -540,6 +580,7 @@ TORCH_LIBRARY(rt, m) {
   m.def("quantize_u8(Tensor color) -> Tensor");
   m.def("assemble_rows(Tensor tiles, int width, int height, int row_block, int out_kind, int root_run=1, "
         "int run=1) -> Tensor");
+  m.def("resolve_samples(Tensor samples, int k, int width, int rows, int out_kind) -> Tensor");
   m.def("status(Tensor(a!) workspace) -> int");
   m.def("workspace_bytes(int n_rays, int max_bounces) -> int", &workspace_bytes);
   // the row-tiled multi-GPU frame (one native call per frame and rank; handles are int64)
@@ -565,6 +606,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("intersect", &intersect);
   m.impl("quantize_u8", &quantize_u8);
   m.impl("assemble_rows", &assemble_rows);
+  m.impl("resolve_samples", &resolve_samples);
   m.impl("status", &status);
 }
 
@@ -578,6 +620,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("intersect", &intersect);
   m.impl("quantize_u8", &quantize_u8);
   m.impl("assemble_rows", &assemble_rows);
+  m.impl("resolve_samples", &resolve_samples);
   m.impl("status", &status);
 }
 
@@ -589,4 +632,5 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("intersect", &intersect_meta);
   m.impl("quantize_u8", &quantize_u8_meta);
   m.impl("assemble_rows", &assemble_rows_meta);
+  m.impl("resolve_samples", &resolve_samples_meta);
 }

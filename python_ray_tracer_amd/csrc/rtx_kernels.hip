@@ -30,6 +30,7 @@
 //                     list of k_render_fast from level 0. Its last block resets the list counter,
 //                     so the workspace is left zeroed for the next call (no per-frame memset).
 //   k_ray_dirs, k_intersect, k_quantize — the remaining boundary functions.
+//   k_resolve         The supersampling box filter of a k x k sample frame (rtx_resolve_samples).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -2467,6 +2468,96 @@ __global__ __launch_bounds__(kBlock) void k_quantize(const T* __restrict__ c, in
   out[3 * i + 2] = quant_u8((double)c[2 * n + i]);
 }
 
+// Supersampling resolve (HipRenderer(samples=k), rtx_resolve_samples): the box filter of a sample
+// frame rendered at (k*width) x (k*n_rows) as RTX_OUT_F64_SOA. Per output pixel and channel the
+// k*k samples of its block are clipped to [0, 1] (as save_image would have clipped that pixel,
+// base.py:147; clip01 sends a NaN to 0 where np.clip keeps it: no sample of a valid scene is NaN),
+// added to 0.0 top row first and left to right, and divided once by k*k: the order is the
+// contract, so the result is the same for every launch shape.
+// A streaming kernel: every sample is read once and every output written once (nontemporal both
+// ways), no LDS, no atomics. A lane's k samples of a row are contiguous; for an even k they start
+// 16-byte aligned (row and plane starts are multiples of 2 doubles), so VEC loads them as double2.
+// K > 0: k at compile time (the loops unroll, all of a pixel's loads are in flight at once);
+// K == 0: k at run time.
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+constexpr int kResolveBlocksPerCu = 8;  // grid cap of k_resolve (blocks per CU), grid-strided beyond it
+// one thread per output pixel and channel plane of the colour outputs, instead of per pixel with its
+// three planes (u8 always takes the pixel: its three bytes are neighbours)
+constexpr bool kResolvePerPlane = false;
+
+template <int K, bool VEC>
+__device__ __forceinline__ double resolve_block(const double* __restrict__ s, int64_t row_stride, int k) {
+  const int kk = K ? K : k;
+  constexpr int kUnroll = K ? K : 1;  // the run-time loops (K == 0) stay rolled
+  double acc = 0.0;
+#pragma unroll kUnroll
+  for (int sy = 0; sy < kk; ++sy) {
+    const double* row = s + sy * row_stride;
+    if (VEC) {
+#pragma unroll kUnroll
+      for (int sx = 0; sx < kk; sx += 2) {
+        const f64x2 v = __builtin_nontemporal_load((const f64x2*)(row + sx));
+        acc = acc + clip01(v.x);
+        acc = acc + clip01(v.y);
+      }
+    } else {
+#pragma unroll kUnroll
+      for (int sx = 0; sx < kk; ++sx) acc = acc + clip01(__builtin_nontemporal_load(row + sx));
+    }
+  }
+  return acc / (double)(kk * kk);
+}
+
+// samples: n_frames x [3][k*n_rows][k*width]; out: n_frames x (width * n_rows pixels as out_kind
+// says). k*k*width*n_rows*n_frames < 2^31 (checked by the host), so pixel indices fit 32 bits; the
+// word offsets (three planes) are 64-bit.
+template <int K, bool VEC, bool PLANE>
+__global__ __launch_bounds__(kBlock) void k_resolve(const double* __restrict__ samples, int k, unsigned width,
+                                                    unsigned n_rows, unsigned n_frames, void* __restrict__ out,
+                                                    int out_kind) {
+  const int kk = K ? K : k;
+  const unsigned n = width * n_rows;                // pixels of a frame
+  const int64_t row_stride = (int64_t)kk * width;   // samples of a sample row
+  const int64_t ns = row_stride * kk * n_rows;      // samples of a plane
+  const int64_t items = (int64_t)n * n_frames * (PLANE ? 3 : 1);
+  for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < items; t += (int64_t)gridDim.x * kBlock) {
+    const unsigned px = PLANE ? (unsigned)(t / 3) : (unsigned)t;  // frame-major pixel index
+    const unsigned f = px / n, i = px - f * n;
+    const unsigned r = i / width, c = i - r * width;
+    const double* s = samples + (int64_t)f * 3 * ns + (int64_t)r * kk * row_stride + (int64_t)c * kk;
+    if (PLANE) {  // colour outputs only
+      const unsigned ch = (unsigned)(t - (int64_t)px * 3);
+      const double v = resolve_block<K, VEC>(s + ch * ns, row_stride, k);
+      const int64_t o = ((int64_t)f * 3 + ch) * n + i;
+      if (out_kind == RTX_OUT_F32_SOA) {
+        __builtin_nontemporal_store((float)v, (float*)out + o);
+      } else {
+        __builtin_nontemporal_store(v, (double*)out + o);
+      }
+      continue;
+    }
+    const double cr = resolve_block<K, VEC>(s, row_stride, k);
+    const double cg = resolve_block<K, VEC>(s + ns, row_stride, k);
+    const double cb = resolve_block<K, VEC>(s + 2 * ns, row_stride, k);
+    if (out_kind == RTX_OUT_F32_SOA) {
+      float* o = (float*)out + (int64_t)f * 3 * n + i;
+      __builtin_nontemporal_store((float)cr, o);
+      __builtin_nontemporal_store((float)cg, o + n);
+      __builtin_nontemporal_store((float)cb, o + 2 * (int64_t)n);
+    } else if (out_kind == RTX_OUT_F64_SOA) {
+      double* o = (double*)out + (int64_t)f * 3 * n + i;
+      __builtin_nontemporal_store(cr, o);
+      __builtin_nontemporal_store(cg, o + n);
+      __builtin_nontemporal_store(cb, o + 2 * (int64_t)n);
+    } else {
+      unsigned char* o = (unsigned char*)out + 3 * (int64_t)px;
+      o[0] = quant_u8(cr);
+      o[1] = quant_u8(cg);
+      o[2] = quant_u8(cb);
+    }
+  }
+}
+
 // Rows of the run of `run` parts from part p of the interleaved row tiling (python_ray_tracer_amd/
 // tiling.py n_local_rows): run * row_block rows of every cycle, the last cycle's prefix.
 __host__ __device__ __forceinline__ int tile_local_rows(int height, int row_block, int n_parts, int p, int run = 1) {
@@ -3147,6 +3238,53 @@ int rtx_quantize_u8(const void* color, int color_kind, int64_t n, uint8_t* out, 
     return fail(RTX_E_ARG, "bad color_kind%s %lld", "", color_kind);
   }
   return check_launch("k_quantize");
+}
+
+int rtx_resolve_samples(const double* samples, int k, int width, int n_rows, int n_frames, void* out, int out_kind,
+                        void* stream) {
+  if (!samples || !out) return fail(RTX_E_ARG, "null pointer argument%s", "");
+  if (k < 1 || k > 8) return fail(RTX_E_ARG, "samples per pixel side must be in 1..8%s, got %lld", "", k);
+  if (width <= 0 || n_rows <= 0 || n_frames <= 0) return fail(RTX_E_ARG, "bad frame geometry%s", "");
+  if (out_kind != RTX_OUT_F32_SOA && out_kind != RTX_OUT_F64_SOA && out_kind != RTX_OUT_U8_HWC)
+    return fail(RTX_E_ARG, "bad out_kind%s %lld", "", out_kind);
+  // k*k*width*n_rows*n_frames < 2^31, without overflowing on the way (nested floor divisions are exact)
+  int64_t room = (((int64_t)1 << 31) - 1) / (k * k);
+  const bool fits = width <= room && n_rows <= (room /= width) && n_frames <= (room /= n_rows);
+  if (!fits) return fail(RTX_E_ARG, "k*k*width*n_rows*n_frames must stay below 2^31 samples per plane%s", "");
+  const bool vec = k % 2 == 0 && (uintptr_t)samples % 16 == 0;
+  const bool plane = kResolvePerPlane && out_kind != RTX_OUT_U8_HWC;
+  const int64_t items = (int64_t)width * n_rows * n_frames * (plane ? 3 : 1);
+  const int64_t cap = (int64_t)device_cus() * kResolveBlocksPerCu, want = (items + kBlock - 1) / kBlock;
+  const dim3 grid((unsigned)(want < cap ? want : cap));
+#define RTX_RESOLVE(K, VEC, PLANE)                                                                             \
+  hipLaunchKernelGGL((k_resolve<K, VEC, PLANE>), grid, dim3(kBlock), 0, (hipStream_t)stream, samples, k,       \
+                     (unsigned)width, (unsigned)n_rows, (unsigned)n_frames, out, out_kind)
+#define RTX_RESOLVE_K(K, VEC)      \
+  do {                             \
+    if (plane) {                   \
+      RTX_RESOLVE(K, VEC, true);   \
+    } else {                       \
+      RTX_RESOLVE(K, VEC, false);  \
+    }                              \
+  } while (0)
+  if (k == 2 && vec) {
+    RTX_RESOLVE_K(2, true);
+  } else if (k == 2) {
+    RTX_RESOLVE_K(2, false);
+  } else if (k == 3) {
+    RTX_RESOLVE_K(3, false);
+  } else if (k == 4 && vec) {
+    RTX_RESOLVE_K(4, true);
+  } else if (k == 4) {
+    RTX_RESOLVE_K(4, false);
+  } else if (vec) {
+    RTX_RESOLVE_K(0, true);
+  } else {
+    RTX_RESOLVE_K(0, false);
+  }
+#undef RTX_RESOLVE_K
+#undef RTX_RESOLVE
+  return check_launch("k_resolve");
 }
 
 int rtx_assemble_rows(const void* tiles, int64_t part_stride_bytes, int n_parts, int width, int height,

@@ -104,7 +104,9 @@ class TileGather:
                  persistent_frames: bool = False, loopback: bool = False, comm_reserve: int | None = None,
                  rows: bool | None = None, shares: tuple | None = None, timed: bool = False) -> None:
         """``native``: drive each frame through rtx_tiles_submit (default: under RCCL with a
-        renderer that has ``submit_tiles``); False keeps torch.distributed.gather. ``persistent_frames``
+        renderer that has ``submit_tiles`` and renders one sample per pixel; a supersampling renderer,
+        ``samples >= 2``, takes torch.distributed.gather, and ``native=True`` with it raises
+        ValueError); False keeps torch.distributed.gather. ``persistent_frames``
         (native root): assemble every frame of a slot into one buffer kept by the slot, so a frame
         returned by finish(slot) is overwritten by that slot's next frame (the bench); otherwise each
         frame gets a new tensor. ``loopback`` (native, one rank): the tile still travels through RCCL
@@ -149,8 +151,15 @@ class TileGather:
                                self.out, self.root_run, self.run)
         self._pending: dict = {}
         self.plan = None
+        # a supersampling renderer (HipRenderer(samples >= 2)) resolves its tile before it travels:
+        # render_tile(into=view) and the gather below move the same bytes as ever; the native plan
+        # (rtx_tiles_submit) renders one sample per pixel
+        supersampled = int(getattr(renderer, "samples", 1)) > 1
+        if native and supersampled:
+            raise ValueError(f"native=True: the native row-tiled plan renders one sample per pixel, the renderer "
+                             f"has samples={renderer.samples}; leave native unset (render_tile and the gather)")
         if native is None:
-            native = not self.gloo and hasattr(renderer, "submit_tiles")
+            native = not self.gloo and hasattr(renderer, "submit_tiles") and not supersampled
         if native:
             self._init_native(dtype, plen, slots, persistent_frames, loopback and self.world == 1,
                               COMM_RESERVE_BLOCKS if comm_reserve is None else int(comm_reserve),

@@ -17,7 +17,7 @@ PKG_DIR = Path(__file__).resolve().parent.parent.parent
 LIB_PATH = Path(os.environ.get("RTX_HIP_LIB", PKG_DIR / "librtx_hip.so"))
 
 # mirrors of include/rtx_hip.h (checked against the library at load time)
-ABI_VERSION = 1
+ABI_VERSION = 2
 HDR_WORDS = 64
 GEOM_WORDS = 8
 MAT_WORDS = 24
@@ -27,6 +27,7 @@ WS_HDR_BYTES = 256
 FAST_MAX_BOUNCES = 6
 UNBOUNDED_LEVELS = 333
 MAX_SPHERES = 1024
+MAX_SAMPLES = 8  # samples per pixel side (rtx_resolve_samples)
 MAGIC = 5527384.0
 UNBOUNDED = -1
 
@@ -97,6 +98,7 @@ EXPORTS = (
     "rtx_tiles_finish",
     "rtx_tiles_destroy",
     "rtx_tiles_timing",
+    "rtx_resolve_samples",
 )
 
 TILES_MAX_SLOTS = 4
@@ -148,6 +150,7 @@ _SIGS = {
     "rtx_tiles_finish": (_i32, [_c_void_p, _i32, _c_void_p]),
     "rtx_tiles_destroy": (_i32, [_c_void_p]),
     "rtx_tiles_timing": (_i32, [_c_void_p, _i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "rtx_resolve_samples": (_i32, [_c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p]),
 }
 
 _lib = None

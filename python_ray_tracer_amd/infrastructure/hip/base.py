@@ -19,6 +19,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
   ``UNBOUNDED_LEVELS`` (333) levels and raises ``RecursionError`` beyond, where Python's recursion
   limit would stop the reference. ``max_bounces=B`` caps it (levels 0..B shaded, level B+1 black).
 * ``color_dtype`` float64 (default, the reference dtype) or float32.
+* ``HipRenderer(samples=k)``: supersampled anti-aliasing, k x k samples per pixel, box-filtered
+  (the reference traces one ray per pixel).
 """
 
 from __future__ import annotations
@@ -32,8 +34,8 @@ import numpy as np
 import torch
 
 from python_ray_tracer_amd.application import Renderer
-from python_ray_tracer_amd.domain import Camera, RGBColor, Vector3D
-from python_ray_tracer_amd.tiling import n_local_rows
+from python_ray_tracer_amd.domain import Camera, RGBColor, Scene3D, Vector3D
+from python_ray_tracer_amd.tiling import check_sample_count, check_samples, n_local_rows
 
 from . import _lib as L
 from .scene_pack import camera_words, pack_key, scene_key
@@ -210,11 +212,28 @@ def _on_device(method):
 
 
 class HipRenderer(Renderer):
-    """MI355X renderer behind the reference ``Renderer`` plugin surface (application.py:7-32)."""
+    """MI355X renderer behind the reference ``Renderer`` plugin surface (application.py:7-32).
+
+    ``samples=k`` (an int in 1..8; default 1, one ray per pixel like the reference) is supersampled
+    anti-aliasing with k x k samples per pixel. The screen is fixed (base.py:130-141), so the k x k
+    samples of every pixel are the pixels of the same scene rendered from the same camera position
+    at (k W, k H): that frame is rendered in float64 by the same kernels into a renderer-owned
+    sample buffer, and a resolve kernel (rtx_resolve_samples) box-filters it into the W x H result
+    of ``render``, ``render_tile``, ``render_batch`` and the ``get_ray_directions`` ->
+    ``raytrace_scene`` pipeline. Every sample is clipped to [0, 1] BEFORE it is averaged, as
+    ``save_image`` would have clipped that pixel (a highlight sample of 190 would otherwise whiten
+    its whole pixel): with ``samples >= 2`` the colour output lies in [0, 1], while ``samples=1``
+    colour stays unclipped. The value of a pixel and channel is the float64 sum of its clipped
+    samples, rows top to bottom and left to right within a row, divided once by k*k; float32
+    output is that value rounded once, uint8 ``(uint8)(255 * value)``. ``stats()`` then counts sample
+    rays (``pixels == k*k*W*H``). ``raytrace_scene`` on materialised or foreign rays and
+    ``shade_hits`` raise ValueError (supersampling needs the camera), as do ``submit_tiles`` and a
+    caller-packed ``blob`` (it holds the W x H camera)."""
 
     def __init__(self, max_bounces: int | None = None, *, color_dtype: torch.dtype = torch.float64,
                  device=None, collect_stats: bool = False, learn_tile_order: bool = True,
-                 fast_textures: bool = True) -> None:
+                 fast_textures: bool = True, samples: int = 1) -> None:
+        samples = check_samples(samples)  # (before the library and the GPU: a bad argument needs neither)
         self._lib = L.load()
         if not torch.cuda.is_available():
             raise RuntimeError("HipRenderer needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path")
@@ -237,6 +256,8 @@ class HipRenderer(Renderer):
         # False defers those pixels to the general kernel (same colours)
         self.fast_textures = bool(fast_textures)
         self._ws = None
+        self.samples = samples
+        self._sample_buf = None  # float64 sample frame(s) of a samples >= 2 render (grow-only, like _ws)
         self._graph_pins: dict = {}  # data_ptr -> tensor a captured launch points at (_tile_launch)
         self.stats_buffer = torch.zeros(L.S_WORDS, dtype=torch.int64, device=self.device) if collect_stats else None
 
@@ -269,6 +290,26 @@ class HipRenderer(Renderer):
             # zero-filled once; every call leaves its counters zeroed again (include/rtx_hip.h)
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def _sample_buffer(self, n: int) -> torch.Tensor:
+        """The first ``n`` words of the renderer's sample buffer: the float64 [3, n/3] sample frame
+        (or [F, 3, ...] frames) a samples >= 2 render writes and rtx_resolve_samples reads. Grow-only
+        like the workspace; pinned for graph replays like the buffers of _tile_launch."""
+        if self._sample_buf is None or self._sample_buf.numel() < n:
+            self._sample_buf = torch.empty(int(n), dtype=torch.float64, device=self.device)
+        if torch.cuda.is_current_stream_capturing():
+            self._graph_pins[self._sample_buf.data_ptr()] = self._sample_buf
+        return self._sample_buf
+
+    def _need_camera(self, what: str) -> None:
+        if self.samples > 1:
+            raise ValueError(f"{what}: HipRenderer(samples={self.samples}) supersamples camera renders only (render, "
+                             "render_tile, render_batch, get_ray_directions -> raytrace_scene); these rays have no "
+                             "pixel grid to refine. Use a samples=1 renderer")
+
+    def _resolve(self, buf: torch.Tensor, width: int, rows: int, frames: int, res: torch.Tensor, kind: int) -> None:
+        L.check(self._lib.rtx_resolve_samples(buf.data_ptr(), self.samples, int(width), int(rows), int(frames),
+                                              res.data_ptr(), kind, self._stream()), "rtx_resolve_samples")
 
     def _general_plan(self, key):
         """(flags, probe) for a camera render identified by ``key`` (scene content, tile, cap).
@@ -341,6 +382,7 @@ class HipRenderer(Renderer):
             cam = normalized_ray_direction.camera
             if _same_camera(cam, scene.camera) and _same_point(ray_origin, cam.position):
                 return HipRGBColor.from_tensor(self.render_tile(scene))
+        self._need_camera("raytrace_scene on materialised or foreign rays")
         return HipRGBColor.from_tensor(self._trace(ray_origin, normalized_ray_direction, scene))
 
     def save_image(self, color, camera: Camera, output_path) -> None:
@@ -364,29 +406,64 @@ class HipRenderer(Renderer):
         ``into``: a contiguous device tensor of that shape and dtype to render into (a
         pre-allocated gather buffer) instead of a new one. ``blob``/``n_spheres``: an already
         packed device scene (checked against its header). ``part_run``: the run of parts
-        part .. part + part_run - 1 as one tile (tiling.tile_rows with run)."""
-        W = int(scene.camera.width)
-        blob, n_spheres, rows, ws, flags, probe, key, order, cost = self._tile_launch(scene, row_block, n_parts, part,
-                                                                                      blob, n_spheres, part_run)
-        n = W * rows
+        part .. part + part_run - 1 as one tile (tiling.tile_rows with run).
+
+        With ``samples = k >= 2`` the tile's k*rows sample rows (the same tiling of the (k W, k H)
+        sample frame in row blocks of k*row_block) are rendered into the sample buffer and resolved
+        into the result; a caller-packed ``blob`` is refused (it holds the W x H camera)."""
+        if self.samples > 1:
+            return self._render_tile_samples(scene, row_block, n_parts, part, out, blob, n_spheres, into, part_run)
+        launch = self._tile_launch(scene, row_block, n_parts, part, blob, n_spheres, part_run)
+        res, kind = self._tile_result(int(scene.camera.width), launch[2], out, into)
+        self._run_tile(scene, row_block, n_parts, part, part_run, launch, res, kind)
+        return res
+
+    def _tile_result(self, W: int, rows: int, out, into):
+        """(tensor, out_kind) a tile of ``rows`` rows is rendered into: ``into`` (checked) or a new one."""
         if out == "u8":
             shape, dtype, kind = (rows, W, 3), torch.uint8, L.OUT_U8_HWC
         else:
-            shape, dtype, kind = (3, n), self.color_dtype, _OUT_KIND[self.color_dtype]
+            shape, dtype, kind = (3, W * rows), self.color_dtype, _OUT_KIND[self.color_dtype]
         if into is None:
-            res = torch.empty(shape, dtype=dtype, device=self.device)
-        else:
-            if (tuple(into.shape) != shape or into.dtype != dtype or into.device != self.device
-                    or not into.is_contiguous()):
-                raise ValueError(f"into: need a contiguous {dtype} tensor of shape {shape} on {self.device}, got "
-                                 f"{into.dtype} {tuple(into.shape)} on {into.device}")
-            res = into
-        L.check(self._lib.rtx_render_camera_sched(blob.data_ptr(), n_spheres, W, int(scene.camera.height), row_block,
+            return torch.empty(shape, dtype=dtype, device=self.device), kind
+        if (tuple(into.shape) != shape or into.dtype != dtype or into.device != self.device
+                or not into.is_contiguous()):
+            raise ValueError(f"into: need a contiguous {dtype} tensor of shape {shape} on {self.device}, got "
+                             f"{into.dtype} {tuple(into.shape)} on {into.device}")
+        return into, kind
+
+    def _run_tile(self, scene, row_block, n_parts, part, part_run, launch, res, kind) -> None:
+        """The camera launch ``launch`` (_tile_launch) of ``scene`` into ``res`` as ``kind``."""
+        blob, n_spheres, rows, ws, flags, probe, key, order, cost = launch
+        L.check(self._lib.rtx_render_camera_sched(blob.data_ptr(), n_spheres, int(scene.camera.width),
+                                                  int(scene.camera.height), row_block,
                                                   n_parts, part, part_run, rows, self._bounces_arg, res.data_ptr(), kind,
                                                   ws.data_ptr(), ws.numel(), self._stats_ptr(), self._stream(), flags,
                                                   _ptr(probe), _ptr(order), _ptr(cost)), "rtx_render_camera")
         self._after_launch(key, probe, cost)
         self._check_status(ws, key if self.stats_buffer is None else None)  # (the full launch key only)
+
+    def _render_tile_samples(self, scene, row_block, n_parts, part, out, blob, n_spheres, into, part_run):
+        """render_tile with samples = k >= 2: the tile of the derived scene (same content, camera
+        position and tiling; camera size (k W, k H), row blocks of k*row_block) through the same
+        launch path (_tile_launch: its plans are keyed by the derived scene) as float64 into the
+        sample buffer, then the resolve into the result, on the same stream."""
+        k = self.samples
+        if blob is not None:
+            raise ValueError(f"blob: a caller-packed scene holds the W x H camera; HipRenderer(samples={k}) packs "
+                             "the sample frame's scene itself")
+        W, H = int(scene.camera.width), int(scene.camera.height)
+        rows = n_local_rows(H, row_block, n_parts, part, part_run)
+        ns = check_sample_count(k, W, rows)
+        res, kind = self._tile_result(W, rows, out, into)
+        if rows == 0:  # an empty tile (a rank's share of a small frame)
+            return res
+        derived = _sample_scene(scene, k)
+        launch = self._tile_launch(derived, k * row_block, n_parts, part, part_run=part_run)
+        assert launch[2] == k * rows, (launch[2], k, rows)
+        buf = self._sample_buffer(3 * ns)
+        self._run_tile(derived, k * row_block, n_parts, part, part_run, launch, buf, L.OUT_F64_SOA)
+        self._resolve(buf, W, rows, 1, res, kind)
         return res
 
     def _after_launch(self, key, probe, cost) -> None:
@@ -467,6 +544,9 @@ class HipRenderer(Renderer):
         """One frame of a row-tiled plan (rtx_tiles_submit, distributed.TileGather): this rank's tile
         of ``scene`` rendered into the plan's slot, the RCCL gather to the root and, there, the
         assembly into ``frame`` (None on peers), all enqueued by one native call."""
+        if self.samples > 1:
+            raise ValueError(f"submit_tiles: the native row-tiled plan renders one sample per pixel; with samples="
+                             f"{self.samples} use TileGather(native=False) (render_tile(into=...) and the gather)")
         blob, n_spheres, rows, ws, flags, probe, key, order, cost = self._tile_launch(scene, row_block, n_parts, part,
                                                                                       part_run=part_run)
         L.check(self._lib.rtx_tiles_submit(plan, int(slot), blob.data_ptr(), n_spheres, self._bounces_arg,
@@ -480,7 +560,10 @@ class HipRenderer(Renderer):
         """Whole frames of several scenes in ONE launch (rtx_render_frames).
         All scenes need the same camera size and sphere count; cameras, spheres and lights may
         differ (an animation). Returns [F, 3, W*H] colour (``out=None``) or [F, H, W, 3] uint8
-        (``out="u8"``); frame f equals ``render_tile(scenes[f], out=out)``."""
+        (``out="u8"``); frame f equals ``render_tile(scenes[f], out=out)`` (with ``samples >= 2``
+        too: the sample frames of all scenes in one launch, then one resolve)."""
+        if self.samples > 1:
+            return self._render_batch_samples(scenes, out)
         key, (blob, F, S, W, H) = self._batch_blob(scenes)
         n = W * H
         if out == "u8":
@@ -494,6 +577,27 @@ class HipRenderer(Renderer):
                                             res.data_ptr(), kind, ws.data_ptr(), ws.numel(), self._stats_ptr(),
                                             self._stream()), "rtx_render_frames")
         self._check_status(ws)
+        return res
+
+    def _render_batch_samples(self, scenes, out):
+        k = self.samples
+        scenes = list(scenes)
+        key, (blob, F, S, Ws, Hs) = self._batch_blob([_sample_scene(sc, k) for sc in scenes])
+        W, H = Ws // k, Hs // k
+        ns = check_sample_count(k, W, H, F)  # all frames' samples of a plane
+        if out == "u8":
+            res = torch.empty((F, H, W, 3), dtype=torch.uint8, device=self.device)
+            kind = L.OUT_U8_HWC
+        else:
+            res = torch.empty((F, 3, W * H), dtype=self.color_dtype, device=self.device)
+            kind = _OUT_KIND[self.color_dtype]
+        buf = self._sample_buffer(3 * ns)
+        ws = self.workspace(ns)
+        L.check(self._lib.rtx_render_frames(blob.data_ptr(), blob.shape[1], F, S, Ws, Hs, self._bounces_arg,
+                                            buf.data_ptr(), L.OUT_F64_SOA, ws.data_ptr(), ws.numel(), self._stats_ptr(),
+                                            self._stream()), "rtx_render_frames")
+        self._check_status(ws)
+        self._resolve(buf, W, H, F, res, kind)
         return res
 
     def _batch_blob(self, scenes):
@@ -546,6 +650,7 @@ class HipRenderer(Renderer):
         ``distance`` (shader.py:63-112, rtx_shade_hits); the reflected rays are level 1 of this
         renderer's bounce cap and see the scene unchanged (another shape's shader shades only the
         level-0 hits, RTX_H_MAT0). Returns [3, n] colour."""
+        self._need_camera("shade_hits")
         si = next((k for k, s in enumerate(scene.shapes) if s is shape), None)
         if si is None:  # scene.shapes.index(shape) in _calculate_shadow (shader.py:126)
             raise ValueError("shape is not in scene.shapes")
@@ -673,6 +778,14 @@ class HipRenderer(Renderer):
     def reset_stats(self) -> None:
         if self.stats_buffer is not None:
             self.stats_buffer.zero_()
+
+
+def _sample_scene(scene, k: int) -> Scene3D:
+    """The scene whose plain render is the sample frame of ``scene`` with k x k samples per pixel:
+    the same shapes, lights and camera position, camera size (k W, k H) (its scene_key is
+    scene_pack.sample_key of the scene's)."""
+    cam = scene.camera
+    return Scene3D(scene.shapes, scene.lights, Camera(cam.position, k * int(cam.width), k * int(cam.height)))
 
 
 def _ptr(t):

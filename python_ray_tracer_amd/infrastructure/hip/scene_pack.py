@@ -119,6 +119,14 @@ def scene_key(scene) -> tuple:
     return static, (_xyz(cam.position), W, H)
 
 
+def sample_key(key: tuple, k: int) -> tuple:
+    """The ``scene_key`` of the sample frame of a supersampled render (HipRenderer(samples=k)): the
+    same static part and camera position at (k W, k H). The screen is fixed (base.py:130-141), so
+    that render covers the same screen with k x k samples per pixel."""
+    static, (pos, W, H) = key
+    return static, (pos, int(k) * W, int(k) * H)
+
+
 def pack_scene(scene) -> np.ndarray:
     """Flatten ``scene`` (shapes, lights, camera) into the float64 blob of include/rtx_hip.h."""
     static, camera = scene_key(scene)

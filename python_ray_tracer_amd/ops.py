@@ -27,6 +27,12 @@ that device's current HIP stream and returns a new tensor):
 * ``rt::assemble_rows(tiles, width, height, row_block, out_kind, root_run=1, run=1)`` — the
   multi-GPU row un-permute of ``tiles`` [ranks, part_len]: rank 0's run of ``root_run`` parts, each
   other rank's run of ``run`` (tiling.runs; 1, 1 = one part per rank).
+* ``rt::resolve_samples(samples, k, width, rows, out_kind)`` — the box filter of supersampled
+  anti-aliasing (HipRenderer(samples=k), rtx_resolve_samples): ``samples`` float64 [3, k*rows*k*width]
+  (a float64 render of the same scene and camera position at k*width x k*rows) or [F, 3, ...];
+  every sample clipped to [0, 1], the k*k of a pixel summed row by row and divided once;
+  [3, rows*width] / [F, 3, rows*width] colour (out_kind 0, 1) or [rows, width, 3] /
+  [F, rows, width, 3] uint8 (out_kind 2). Needs no workspace and raises on a short ``samples``.
 * ``rt::status(workspace)`` — reads and clears the sticky RTX_ST_* flags (1 stack overflow,
   2 deferred-list overflow, 4 bad scene); synchronises.
 * ``rt::workspace_bytes(n_rays, max_bounces)``.
@@ -55,7 +61,7 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "status", "workspace_bytes",
+       "resolve_samples", "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
        "comm_unique_id", "comm_init", "comm_destroy", "tiles_create", "tiles_submit", "tiles_finish",
        "tiles_destroy")

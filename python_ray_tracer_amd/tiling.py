@@ -38,6 +38,46 @@ def tile_rows(height: int, row_block: int, n_parts: int, part: int, run: int = 1
     return (lr // own) * (n_parts * row_block) + part * row_block + lr % own
 
 
+MAX_SAMPLES = 8  # samples per pixel side of a supersampled render (rtx_resolve_samples)
+SAMPLE_LIMIT = 1 << 31  # k*k*width*rows*frames stays below it: the resolve indexes pixels in 32 bits
+
+
+def check_samples(k) -> int:
+    """``k``, the samples per pixel side of a supersampled render: an int in 1..MAX_SAMPLES."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_SAMPLES:
+        raise ValueError(f"samples must be an int in 1..{MAX_SAMPLES} (samples per pixel side), got {k!r}")
+    return int(k)
+
+
+def sample_tiling(height: int, row_block: int, k: int) -> tuple:
+    """(height, row_block) of the sample frame of a supersampled render: k sample rows per row, so
+    row blocks of k * row_block sample rows. With the same n_parts, part and run, the tile's
+    sample rows are the k rows of each of its rows, in its local order: local sample row
+    k * lr + sy is global sample row k * tile_rows[lr] + sy. A partial last block stays whole:
+    k H - m k rb = k (H - m rb)."""
+    return int(k) * int(height), int(k) * int(row_block)
+
+
+def n_sample_rows(height: int, row_block: int, n_parts: int, part: int, run: int = 1, k: int = 1) -> int:
+    """Sample rows of a tile of a supersampled render: k * n_local_rows."""
+    return n_local_rows(*sample_tiling(height, row_block, k), n_parts, part, run)
+
+
+def sample_tile_rows(height: int, row_block: int, n_parts: int, part: int, run: int = 1, k: int = 1) -> np.ndarray:
+    """Global sample row of each local sample row of a tile of a supersampled render."""
+    return tile_rows(*sample_tiling(height, row_block, k), n_parts, part, run)
+
+
+def check_sample_count(k: int, width: int, rows: int, frames: int = 1) -> int:
+    """Samples per colour plane of a supersampled render, k*k*width*rows*frames; ValueError at
+    SAMPLE_LIMIT (2^31) and beyond, where rtx_resolve_samples refuses."""
+    n = int(k) * int(k) * int(width) * int(rows) * int(frames)
+    if n >= SAMPLE_LIMIT:
+        raise ValueError(f"samples={k}: {k}x{k} samples of {width}x{rows} pixels x {frames} frame(s) = {n} "
+                         f"samples per plane, the resolve takes fewer than 2^31; render row tiles (render_tile)")
+    return n
+
+
 def runs(world: int, root_run: int = 1, run: int = 1):
     """(n_parts, [(first part, run) per rank]) of the shares: rank 0 renders parts [0, root_run),
     rank i >= 1 parts [root_run + (i - 1) run, root_run + i run)."""

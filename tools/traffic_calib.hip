@@ -11,9 +11,17 @@
 //   k_stream16   16 bytes per lane, consecutive lanes consecutive (the guide's calibrated case), same
 //                byte count
 //   k_read_f64   8-byte loads per lane of a 24,883,200-byte buffer (summed into one word per block)
+//
+//   tools/traffic_calib read BYTES [STEPS]   times k_read_f64 alone over a BYTES buffer (HIP events, 5
+//                warm-up launches, STEPS timed ones, default 30) and prints one JSON line with the median
+//                time and rate: the streaming read that tools/ssaa_bench.py puts beside the resolve kernel
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
 
 constexpr int W = 1920, H = 1080;
 
@@ -42,7 +50,40 @@ __global__ __launch_bounds__(256) void k_read_f64(const double* in, long long n,
   if ((threadIdx.x & 63) == 0 && v == 12345.678) sink[0] = v;  // never true: keeps the loads alive
 }
 
-int main() {
+// `read BYTES [STEPS]`: the timed streaming read
+int timed_read(long long bytes, int steps) {
+  void *b = nullptr, *s = nullptr;
+  hipEvent_t e0, e1;
+  if (bytes < 8 || steps < 1 || hipMalloc(&b, bytes) != hipSuccess || hipMalloc(&s, 64) != hipSuccess ||
+      hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    fprintf(stderr, "bad arguments, or hipMalloc / hipEventCreate failed\n");
+    return 1;
+  }
+  (void)hipMemset(b, 0, bytes);
+  const long long n = bytes / 8;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  std::vector<float> ms;
+  for (int rep = 0; rep < 5 + steps; ++rep) {
+    (void)hipEventRecord(e0, 0);
+    hipLaunchKernelGGL(k_read_f64, grid, dim3(256), 0, 0, (const double*)b, n, (double*)s);
+    (void)hipEventRecord(e1, 0);
+    float t = 0.f;
+    if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess) {
+      fprintf(stderr, "kernel failed\n");
+      return 1;
+    }
+    if (rep >= 5) ms.push_back(t);
+  }
+  std::sort(ms.begin(), ms.end());
+  const double med = ms[ms.size() / 2];
+  printf("{\"kernel\": \"k_read_f64\", \"bytes\": %lld, \"steps\": %d, \"median_us\": %.2f, \"min_us\": %.2f, "
+         "\"max_us\": %.2f, \"GBps\": %.1f}\n",
+         n * 8, steps, med * 1e3, ms.front() * 1e3, ms.back() * 1e3, n * 8 / (med * 1e-3) / 1e9);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc >= 3 && !strcmp(argv[1], "read")) return timed_read(atoll(argv[2]), argc >= 4 ? atoi(argv[3]) : 30);
   const long long bytes = 3LL * W * H * 4;
   void *a = nullptr, *b = nullptr, *s = nullptr;
   if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess || hipMalloc(&s, 64) != hipSuccess) {
