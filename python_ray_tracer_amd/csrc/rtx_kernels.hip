@@ -8,27 +8,28 @@
 // -ffp-contract=off because NumPy never fuses a multiply into an add.
 //
 // Kernels
-//   k_render_fast<B, LDS>  B <= RTX_FAST_MAX_BOUNCES. The reference's recursion
+//   k_render_fast<B, LDS, DEEP>  The reference's recursion
 //                     raytrace_scene -> create -> _calculate_reflection -> raytrace_scene
 //                     (base.py:91-121, shader.py:63-161) becomes an in-register loop over bounce
-//                     levels. For every non-terminal level a compile-time-sized shift register keeps
-//                     the INPUTS of that level's colour terms (max(N.L,0), the dome sum, the specular,
-//                     N.V, the hit sphere and its checker bit: 4 doubles + 1 int); the fold from the
-//                     deepest level recomputes A and I from them with the same instructions and
-//                     applies the reference association
-//                         col_k = ((A_k + (spec_k + col_{k+1}*0.5)*g_k) + I_k)      (shader.py:106-110)
-//                     exactly. Sphere geometry is read by the wave-uniform loops through the scalar
-//                     cache (s_load); the per-lane hit-sphere/material records come from an LDS copy
-//                     of the scene table (LDS = S <= kLdsMaxSpheres). Scenes of >= 8 spheres carry
-//                     a tree of boxes that the loops walk wave-uniformly (exact culling). Tile rows
-//                     are dispatched bottom-up (longest work first). A ray that meets a tie (two
-//                     shapes at the same nearest distance, base.py:103 — both get shaded and summed)
-//                     or, under a cap above 8 or none, a chain longer than kDeepLevels levels is
-//                     appended to a deferred list.
+//                     levels that accumulates the chain's colour forwards: every level adds its own
+//                     colour with a black reflection, weighted by the chain's throughput
+//                         col = sum_k T_k L_k,  T_0 = 1,  T_{k+1} = (T_k * 0.5) * g_k
+//                     (shader.py:106-110 reassociated), so nothing is kept per level. Sphere geometry
+//                     is read by the wave-uniform loops through the scalar cache (s_load); the per-lane
+//                     hit-sphere/material records come from an LDS copy of the scene table (LDS = S <=
+//                     kLdsMaxSpheres). Scenes of >= 8 spheres carry a tree of boxes that the loops walk
+//                     wave-uniformly (exact culling). Tile rows are dispatched bottom-up (longest work
+//                     first). A cap B <= RTX_FAST_MAX_BOUNCES ends the chain at level B (DEEP 0). Under
+//                     a larger cap or none, the DEEP first pass (DEEP 1) follows a chain to level
+//                     kFirstPassLevels (30) and defers what is still alive with a resume record; one
+//                     continuation pass (DEEP 2) takes those chains on to level kDeepLevel3 (60) and
+//                     defers again. A ray that meets a tie (two shapes at the same nearest distance,
+//                     base.py:103 — both get shaded and summed) is appended to the deferred list too.
 //   k_render_general  Any bounce cap, ties included: an explicit depth-first walk of the ray tree
-//                     with per-worker frame stacks in the workspace (HBM). Renders the deferred
-//                     list of k_render_fast from level 0. Its last block resets the list counter,
-//                     so the workspace is left zeroed for the next call (no per-frame memset).
+//                     with per-worker frame stacks in the workspace (HBM). Renders the ties of the
+//                     deferred list from level 0 and resumes its deep chains from their records. Its
+//                     last block resets the list counter, so the workspace is left zeroed for the
+//                     next call (no per-frame memset).
 //   k_ray_dirs, k_intersect, k_quantize — the remaining boundary functions.
 //   k_resolve         The supersampling box filter of a k x k sample frame (rtx_resolve_samples).
 #include <hip/hip_ext.h>
@@ -69,32 +70,20 @@ constexpr int kMaxFetch = 32;   // tile counters (one 128-byte line each) shared
 // more blocks), or ties and deep chains (A/B for unbounded renders: 4096, 16384, 65536)
 constexpr int kDeferredWorkers = 4096;
 constexpr int kDeepWorkers = 16384;
-constexpr bool kLevelsInLds = true;  // capped kernels with B <= kLevelsLdsMaxB keep their levels' colour inputs in LDS
-constexpr int kLevelsLdsMaxB = 6;    // the deepest cap with LDS level slots
-constexpr int kLevelsLdsSlots = 3;   // levels kept in LDS; deeper ones (B = 4) in a register slot
-constexpr int kB5Slots = 2;          // LDS level slots of the B >= 5 kernels (the others in a register shift)
-constexpr int kB5Waves = 4;          // their waves/SIMD
-constexpr int kLvWaves = 5;          // waves/SIMD of the kernels with LDS level slots (96 VGPRs; 5 blocks fit up to 17 spheres)
-constexpr int kLvWavesSmall = 5;     // ... and of their TREE = false instantiations (scenes below kTreeMinSpheres)
-constexpr int kDeepLvMaxSpheres = 32;  // DEEP kernels with LDS level slots up to this many spheres (3 blocks of 54 KB per CU)
 constexpr int kDeepWaves = 4;        // waves/SIMD of the persistent DEEP kernel (with the beam at 3 its persistent kernel takes
                                      // 134 VGPRs; at 4, 128: A/B r6ap, unbounded C4 -14%)
 constexpr int kDeepWavesTile = 5;    // ... of the one-tile first passes (TP 1 and 0; A/B r6ar, unbounded: C3 -5.1%,
                                      // C2 -2.0%, C2main -5.0% against 4, the persistent C4 +-0)
-constexpr int kFastWavesPerSimd = 4; // __launch_bounds__ min waves per SIMD otherwise: <=128 VGPRs (A/B: faster than 3 waves without spills)
-// Capped kernels (B <= RTX_FAST_MAX_BOUNCES): the bounce chain's colour is accumulated forwards,
-// col = sum_k T_k L_k with T_0 = 1, T_{k+1} = (T_k * 0.5) * g_k and L_k level k's colour with a
-// black reflection, instead of storing every non-terminal level's colour inputs and folding them
-// back from the deepest level (the reference's association, shader.py:106-110: col_k = ((A_k +
-// (spec_k + col_{k+1} * 0.5) * g_k) + I_k)). Same terms, reassociated: the result moves by a few
-// ulp of the colour (<= ~1e-13 absolute at the brightest unclipped values, under the 1e-12 parity
-// bar), and no level's inputs live in LDS slots or registers across the chain: C4's B = 5 kernel
-// kept three levels in a register shift (27 VGPRs, the bulk of its 41 spilled) beside two LDS slots.
-// The DEEP kernels keep the backward fold (their resume records carry the levels' inputs).
-// A/B r5c (one box, tools/ab.py, frames identical): C2 55.20 -> 52.94 us (-4.1%), C4 2,055 -> 1,874 us
-// (-8.8%: 41 spilled VGPRs -> 0), C3 273.1 -> 265.7 us (-2.7%, at 5 waves/SIMD; 283.9 at 4)
-constexpr bool kForwardFold = true;
-constexpr int kFwdWavesPersist = 4;  // waves/SIMD of the forward-fold persistent kernels (TP 2; C4: 5 waves 2,025 us)
+// Every kernel accumulates the bounce chain's colour forwards, col = sum_k T_k L_k with T_0 = 1,
+// T_{k+1} = (T_k * 0.5) * g_k and L_k level k's colour with a black reflection, instead of storing
+// every non-terminal level's colour inputs and folding them back from the deepest level (the
+// reference's association, shader.py:106-110: col_k = ((A_k + (spec_k + col_{k+1} * 0.5) * g_k) +
+// I_k)). Same terms, reassociated: the result moves by a few ulp of the colour (<= ~1e-13 absolute
+// at the brightest unclipped values, under the 1e-12 parity bar), and no level's inputs live in LDS
+// or registers across the chain. A/B r5c against the backward fold (one box, tools/ab.py, frames
+// identical): C2 55.20 -> 52.94 us (-4.1%), C4 2,055 -> 1,874 us (-8.8%: 41 spilled VGPRs -> 0),
+// C3 273.1 -> 265.7 us (-2.7%, at 5 waves/SIMD; 283.9 at 4)
+constexpr int kFwdWavesPersist = 4;  // waves/SIMD of the capped persistent kernels (TP 2; C4: 5 waves 2,025 us)
 constexpr int kFwdWaves = 5;         // ... of the culled one-tile-per-block kernels (TP 1; C3: 4 waves 283.9 us)
 // ... and of their launches of at least kWavesLargeMinPixels pixels (A/B r6aw, 6 waves against 5: C3 (8.3 M
 // pixels) -3.3%, C5's 32-frame launches -3.5%, but one 1080p frame of C5's scene +4%: 80 VGPRs spill)
@@ -136,21 +125,7 @@ constexpr int kFrameWords = 20;  // general-kernel stack frame (float64 words)
 constexpr int kFetchStride = 32;  // uint32 words between counters
 constexpr int kSphWords = RTX_GEOM_WORDS + RTX_MAT_WORDS;
 constexpr int kLdsMaxSpheres = 128;  // scene table staged in LDS up to this size (32 KiB)
-// The colour inputs of the non-terminal levels (4 doubles + the key per level and lane) go to LDS
-// slots indexed by the level instead of a register shift register (no moves per level, 27 fewer
-// live VGPRs): [B][4][kFastBlock] doubles + [B][kFastBlock] ints after the scene table.
-template <int B, bool LDS, bool DEEP>
-constexpr bool levels_in_lds() { return kLevelsInLds && LDS && !DEEP && !kForwardFold && B > 0 && B <= kLevelsLdsMaxB; }
-// the DEEP variant (3 waves/SIMD: 3 blocks per CU) keeps all its levels in LDS
-template <bool DEEP = false>
-__host__ __device__ constexpr int level_lds_slots(int B) {
-  return DEEP || B < kLevelsLdsSlots ? B : B >= 5 ? kB5Slots : kLevelsLdsSlots;
-}
-template <bool DEEP = false, bool TREE = true>
-__host__ __device__ constexpr size_t level_lds_bytes(int B) {
-  return (size_t)level_lds_slots<DEEP>(B) * fast_block<TREE>() * (4 * 8 + 4);
-}
-// The one-tile culled kernels (TP 1, capped: the forward fold) accumulate the pixel colour in LDS
+// The one-tile culled kernels (TP 1, capped) accumulate the pixel colour in LDS
 // after the scene table ([3][block] doubles, each lane its own slots) instead of three VGPR pairs:
 // at 96 VGPRs (5 waves/SIMD) one of them spilled to scratch on every level (C3 traffic 1.5x).
 constexpr size_t kColourLdsBytes = 3 * sizeof(double) * 256;
@@ -160,7 +135,6 @@ constexpr int kGeneralTreeMin = 32;
 // scenes of fewer spheres never carry a culling tree (scene_pack.BVH_MIN_SPHERES): the fast kernel's
 // TREE = false instantiations serve them
 constexpr int kTreeMinSpheres = 8;
-constexpr size_t kLdsBytesPerCu = 160 * 1024;  // gfx950
 
 // Wave-uniform loads through the scalar cache: the constant address space makes hipcc emit s_load
 // even though the kernel also stores (it cannot prove the scene blob is not aliased otherwise).
@@ -232,33 +206,26 @@ constexpr int kFrameShift = 34;
 constexpr int kRaysShift = 50;
 constexpr int kHitsShift = 57;
 constexpr int kLevelMask = 0x7F;  // 7-bit level fields (level + 1)
-// Resume record of a pixel deferred for depth at level L = kDeepLevels: the next level's ray
-// (origin, direction) and the colour inputs (dli, di, spec, va, key) of levels 0..L; the general
-// kernel continues the chain at level L + 1 instead of re-rendering it from level 0.
-constexpr int kRecLevelWords = 5;
-// With the forward fold (kForwardFold) the DEEP kernels' record is the next ray, the colour
-// accumulated through level L and the throughput of level L + 1: 10 words whatever L.
-__host__ __device__ constexpr int rec_words(int level) {
-  return kForwardFold ? 10 : 6 + kRecLevelWords * (level + 1);
-}
-// the first DEEP pass's record level (forward fold: a runtime level, no storage per level; A/B r5zo
+// Resume record of a pixel deferred for depth at level L: the next level's ray (origin, direction),
+// the colour accumulated through level L and the throughput of level L + 1, 10 words whatever L;
+// the continuation pass and the general kernel continue the chain at level L + 1 instead of
+// re-rendering it from level 0.
+constexpr int kRecWords = 10;
+// the first DEEP pass's record level (a runtime level, no storage per level; A/B r5zo
 // on unbounded renders end to end, 5 / 9 / 14 levels: C2 98.7 / 93.7 / 77.8 us, C3 378 / 367 / 326 us,
 // C4 2,514 / 2,485 / 2,440 us; r5zp, 14 / 16 / 30 with the continuation pass to 60: C2 77.8 / 77.5 /
 // 77.4, C3 327 / 310 / 304, C4 2,437 / 2,380 / 2,166 us)
 constexpr int kFirstPassLevels = 30;
-constexpr int kDeepLevel2 = 2 * kDeepLevels + 1;  // deferral level of the first continuation pass
-constexpr int kDeepLevel3 = kForwardFold ? 60 : 3 * kDeepLevels + 2;  // ... and of the second (forward: the one)
-static_assert(!kForwardFold || (kFirstPassLevels >= kDeepLevels && kFirstPassLevels < kDeepLevel3),
-              "first-pass record level");
+constexpr int kDeepLevel3 = 60;  // the continuation pass's record level
+static_assert(kFirstPassLevels >= kDeepLevels && kFirstPassLevels < kDeepLevel3, "first-pass record level");
 static_assert(kDeepLevel3 + 2 < kLevelMask, "deferred-entry level fields hold 7 bits");
-// Resume-record capacities per deferral level (pass 0: the first pass's level kDeepLevels;
-// 1, 2: the continuation passes'): at least 2^18 / 2^16 / 2^14, or one per 32 / 256 / 2048 pixels,
-// whichever is more. Chains alive at level 5 are 0.2-1.4% of the pixels in the bench scenes (C4:
-// 467,657 of 33.2 M), far fewer at 11 and 17. An entry beyond the capacity is re-rendered from
-// level 0 by the general kernel: correct, but slow.
-__host__ __device__ constexpr int64_t records_cap(int64_t n, int pass) {
-  const int64_t lo = int64_t(1) << (18 - 2 * pass);
-  const int64_t by_n = n / (int64_t(32) << (3 * pass));
+// Resume-record capacities of the first pass and (cont) of the continuation pass: at least 2^18 /
+// 2^14, or one per 32 / 2048 pixels, whichever is more. Chains alive at level 5 are 0.2-1.4% of the
+// pixels in the bench scenes (C4: 467,657 of 33.2 M), far fewer at the record levels. An entry
+// beyond the capacity is re-rendered from level 0 by the general kernel: correct, but slow.
+constexpr int64_t records_cap(int64_t n, bool cont) {
+  const int64_t lo = int64_t(1) << (cont ? 14 : 18);
+  const int64_t by_n = n / (cont ? 2048 : 32);
   const int64_t want = by_n > lo ? by_n : lo;
   return n < want ? n : want;
 }
@@ -1644,7 +1611,12 @@ __device__ __forceinline__ int lane_id_fresh() {
   return l;
 }
 
-__device__ __forceinline__ void write_out(const Params& p, int64_t i, double r, double g, double b) {
+// (the colour by reference: fast_tile's accumulators then stay memory objects until this call is
+// inlined, and are promoted to registers together with the level's colour; taken by value they are
+// promoted one pass earlier and the one-tile culled kernels come out scheduled differently: A/B,
+// identical frames, C3 +0.4%)
+__device__ __forceinline__ void write_out(const Params& p, int64_t i, const double& r, const double& g,
+                                          const double& b) {
   // the frame is written once and never read back by the kernel: streaming (nontemporal) stores
   // (A/B, identical output: C5 -1.5..-1.9%, C3 -0.9%, C2 -0.4..-0.8%)
   if (p.out_kind == RTX_OUT_F32_SOA) {
@@ -1681,14 +1653,14 @@ __device__ __forceinline__ void stat_wave(unsigned long long* st, int word) {
 
 // One block tile: (bx, by) in camera mode, block bx of 256 rays in explicit-ray mode, 256 entries
 // of in_list in continuation mode. `first`: the block's first tile, whose level-0 nearest-hit test
-// overlaps the LDS staging of the scene table. DEEP (caps above 8 or none): chains still alive
-// after B levels are deferred with a resume record, and the continuation mode exists; the capped
-// instantiations compile none of it.
+// overlaps the LDS staging of the scene table. DEEP (caps above RTX_FAST_MAX_BOUNCES or none): chains
+// still alive at the launch's record level are deferred with a resume record, and the continuation
+// mode exists; the capped instantiations compile none of it.
 // IMG: image-textured spheres are shaded here (the texel lookup compiled in, RTX_F_IMAGES launches)
 // instead of deferred to the general kernel.
 // NSPH > 0: the scene has exactly NSPH spheres, a compile-time count (the timed small-scene kernels,
 // rtx_small.hip: their sphere loops unroll; A/B r6b, C2 -2.7%); 0: p.nsph at run time.
-template <int B, bool LDS, int DEEP, bool LVL, bool STATS, bool TREE, bool BEAM, bool IMG = false, int NSPH = 0>
+template <int B, bool LDS, int DEEP, bool STATS, bool TREE, bool BEAM, bool IMG = false, int NSPH = 0>
 __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool first, const double* lds_tab,
                                           bool wave_tile = false) {
   constexpr int FB = fast_block<TREE>();  // threads per block of this instantiation
@@ -1702,7 +1674,7 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
   int64_t i = 0;
   bool active;
   int kb = 0;                  // absolute level of this launch's first ray (mode 2: the resumed level)
-  const double* rin = nullptr;  // mode 2: the chain's resume record (levels 0..kb-1)
+  const double* rin = nullptr;  // mode 2: the chain's resume record
   int col = 0, lr = 0;         // mode 0: the pixel's column and local row
   // WX x WY waves per block; wave w -> WW x WH sub-tile, lane -> (l % WW, l / WW)
   // (wave_tile: (bx, by) is this wave's own WW x WH tile; TREE only, so WW = kWaveW there)
@@ -1737,7 +1709,7 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
       i = (int64_t)(e & ((uint64_t(1) << kFrameShift) - 1));
       const int rt = (int)((e >> kRaysShift) & kLevelMask) - 1, ht = (int)((e >> kHitsShift) & kLevelMask) - 1;
       if (rt == p.in_level && ht == rt && item < p.in_rec_cap) {
-        rin = p.in_rec + item * rec_words(p.in_level);
+        rin = p.in_rec + item * kRecWords;
         kb = rt + 1;
       } else {  // a tie, or a chain without a record: on to the general kernel unchanged
         append_deferred(p, e);
@@ -1807,7 +1779,7 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
     if (first) __syncthreads();
   }
   if (!active) return;
-  constexpr bool CL = kForwardFold && !DEEP && LDS && TREE && !BEAM;  // colour in LDS (kColourLdsBytes)
+  constexpr bool CL = !DEEP && LDS && TREE && !BEAM;  // colour in LDS (kColourLdsBytes)
   static_assert(!CL || 3 * sizeof(double) * FB == kColourLdsBytes, "colour LDS");
   double* const cl = CL ? const_cast<double*>(lds_tab) + nsph * kSphWords + threadIdx.x : nullptr;
   if constexpr (CL) {
@@ -1816,23 +1788,10 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
     cl[2 * FB] = 0.0;
   }
 
-  // shift register of the non-terminal levels' colour inputs (slot 0 = most recent level), or,
-  // levels_in_lds, LDS slots indexed by the level (slot j = level kb + j)
-  constexpr bool LV = LVL && LDS && B > 0 && !kForwardFold;
-  constexpr int NS = B > 0 ? B : 1;
-  constexpr int NL = LV ? level_lds_slots<(DEEP != 0)>(B) : 0;  // levels 0..NL-1 in LDS, NL..B-1 in registers
-  constexpr int NR = LV ? (B > NL ? B - NL : 1) : NS;
-  double sDli[NR], sDi[NR], sSpec[NR], sVa[NR];
-  int sKey[NR];  // hit sphere | checker bit << 16
-  double* const lvd = LV ? const_cast<double*>(lds_tab) + nsph * kSphWords : nullptr;  // [NL][4][FB]
-  int* const lvk = LV ? (int*)(lvd + NL * 4 * FB) : nullptr;                          // [NL][FB]
-  const int lt = threadIdx.x;
-  int depth = 0;
+  // the colour accumulated level by level, thr = T_k
   double cr = 0.0, cg = 0.0, cb = 0.0;
-  // kForwardFold (capped kernels): colour accumulated level by level, thr = T_k
-  constexpr bool FWD = kForwardFold;
   double thr = 1.0;
-  if constexpr (FWD && DEEP == 2) {  // a continued chain: its colour so far and the next level's weight
+  if constexpr (DEEP == 2) {  // a continued chain: its colour so far and the next level's weight
     if (rin) {
       cr = rin[6];
       cg = rin[7];
@@ -1844,10 +1803,7 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
   int rays_through = 0, hits_through = -1;  // per-level counts already made for this pixel
 
   for (int k = 0;; ++k) {
-    if (hit < 0) {  // nothing hit: NumpyRGBColor(0, 0, 0) (base.py:100)
-      if constexpr (!FWD) cr = cg = cb = 0.0;  // (forwards: a black reflection adds nothing)
-      break;
-    }
+    if (hit < 0) break;  // nothing hit: NumpyRGBColor(0, 0, 0) (base.py:100), a black reflection adds nothing
     if (tie) {  // several shapes shaded and summed: the general kernel takes this ray
       deferred = true;
       rays_through = kb + k;
@@ -1874,43 +1830,10 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
     const bool weighted = s.lit && s.g != 0.0;
     // the cap itself (absolute level; a continuation pass may run into a cap of 9 or 10)
     const bool at_cap = DEEP && p.max_bounces >= 0 && kb + k >= p.max_bounces;
-    if (!FWD && DEEP && weighted && k >= B && !at_cap) {  // the chain goes on beyond this kernel's levels
-      // k == B: levels kb..kb+B-1 are in the shift register (slot j = level kb+B-1-j), kb+B in s
-      deferred = true;
-      appended = true;
-      rays_through = hits_through = kb + B;
-      const int64_t slot =
-          append_deferred(p, deferred_entry(DEEP == 2 || !TREE ? i : pixel_index(lane_id_fresh()), p.frame, kb + B, kb + B));
-      if (p.drec && slot >= 0 && slot < p.rec_cap && kb + B == p.drec_level) {
-        double* rec = p.drec + slot * rec_words(kb + B);
-        double rx = dx, ry = dy, rz = dz;
-        reflect_dir(rx, ry, rz, s.nx, s.ny, s.nz);
-        rec[0] = s.qx; rec[1] = s.qy; rec[2] = s.qz;
-        rec[3] = rx; rec[4] = ry; rec[5] = rz;
-        for (int w = 0; w < kRecLevelWords * kb; ++w) rec[6 + w] = rin[6 + w];  // levels 0..kb-1
-        double* lv = rec + 6 + kRecLevelWords * (kb + B);
-        lv[0] = s.dli; lv[1] = s.di; lv[2] = s.spec; lv[3] = s.va; lv[4] = (double)level_key(hit, s.tk);
-        if constexpr (LV) {  // LDS slot d = level kb + d (a DEEP kernel keeps all B levels there)
-          static_assert(!LV || !DEEP || NL == B, "DEEP level slots");
-          for (int d = 0; d < NL; ++d) {
-            const double* const l = lvd + (d * 4) * FB + lt;
-            double* lj = rec + 6 + kRecLevelWords * (kb + d);
-            lj[0] = l[0]; lj[1] = l[FB]; lj[2] = l[2 * FB]; lj[3] = l[3 * FB];
-            lj[4] = (double)lvk[d * FB + lt];
-          }
-        } else if constexpr (B > 0) {
-#pragma unroll
-          for (int j = 0; j < NS; ++j) {
-            double* lj = rec + 6 + kRecLevelWords * (kb + B - 1 - j);
-            lj[0] = sDli[j]; lj[1] = sDi[j]; lj[2] = sSpec[j]; lj[3] = sVa[j]; lj[4] = (double)sKey[j];
-          }
-        }
-      }
-      break;
-    }
-    if (FWD) {
+    {  // (a scope of its own: lr_, lg_, lb_ and kmax end before the next level's search. The DEEP kernels'
+       // register allocation follows it: without the braces their spills move by a few VGPRs either way)
       // this level's colour with a black reflection, weighted by the chain's throughput (at level 0
-      // cr = 0 + 1 * L_0 = L_0 exactly: a chain of one level is bit-identical to the backward fold)
+      // cr = 0 + 1 * L_0 = L_0 exactly: a chain of one level has the reference's association)
       const double* tab = LDS ? (const double*)lds_tab : p.scene + RTX_HDR_WORDS;
       double lr_, lg_, lb_;
       hit_color<IMG>(tab + nsph * RTX_GEOM_WORDS + hit * RTX_MAT_WORDS, sc, s.dli, s.di, s.tk, s.lit, weighted, s.spec,
@@ -1924,8 +1847,8 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
         cg = __builtin_fma(thr, lg_, cg);
         cb = __builtin_fma(thr, lb_, cb);
       }
-      // a DEEP launch goes on to its record level (the first pass: level B; the continuation pass:
-      // kDeepLevel3, the registers holding nothing per level), then defers the chain with a record
+      // a DEEP launch goes on to its record level (the first pass: kFirstPassLevels; the continuation
+      // pass: kDeepLevel3, the registers holding nothing per level), then defers the chain with a record
       const int kmax = DEEP ? p.drec_level - kb : B;
       if (DEEP && weighted && k >= kmax && !at_cap) {  // the chain goes on beyond this launch's levels
         deferred = true;
@@ -1934,7 +1857,7 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
         const int64_t slot = append_deferred(p, deferred_entry(DEEP == 2 || !TREE ? i : pixel_index(lane_id_fresh()),
                                                                p.frame, kb + kmax, kb + kmax));
         if (p.drec && slot >= 0 && slot < p.rec_cap) {
-          double* rec = p.drec + slot * rec_words(kb + kmax);
+          double* rec = p.drec + slot * kRecWords;
           double rx = dx, ry = dy, rz = dz;
           reflect_dir(rx, ry, rz, s.nx, s.ny, s.nz);
           rec[0] = s.qx; rec[1] = s.qy; rec[2] = s.qz;
@@ -1946,40 +1869,8 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
       }
       if (!weighted || k >= kmax || at_cap) break;
       thr = (thr * 0.5) * s.g;  // the reflection's weight, (R * 0.5) * g (shader.py:106)
-    } else if (!weighted || k >= B || at_cap) {
-      // terminal level: the reflection is black (capped: R = 0) or multiplied by zero
-      const double* tab = LDS ? (const double*)lds_tab : p.scene + RTX_HDR_WORDS;
-      hit_color<IMG>(tab + nsph * RTX_GEOM_WORDS + hit * RTX_MAT_WORDS, sc, s.dli, s.di, s.tk, s.lit, weighted, s.spec,
-                s.va, 0.0, 0.0, 0.0, cr, cg, cb);
-      break;
     }
-    // push this level's colour inputs; the reflected ray becomes the next level
-    if constexpr (FWD) {
-      // (nothing to keep: the level's colour is already in cr, cg, cb)
-    } else if constexpr (LV) {
-      if (NL == B || k < NL) {  // k: wave-uniform, == depth of every active lane
-        double* const l = lvd + (depth * 4) * FB + lt;
-        l[0] = s.dli; l[FB] = s.di; l[2 * FB] = s.spec; l[3 * FB] = s.va;
-        lvk[depth * FB + lt] = level_key(hit, s.tk);
-      } else {  // levels beyond the LDS slots: a register shift (slot 0 = the most recent)
-#pragma unroll
-        for (int j = NR - 1; j > 0; --j) {
-          sDli[j] = sDli[j - 1]; sDi[j] = sDi[j - 1]; sSpec[j] = sSpec[j - 1]; sVa[j] = sVa[j - 1];
-          sKey[j] = sKey[j - 1];
-        }
-        sDli[0] = s.dli; sDi[0] = s.di; sSpec[0] = s.spec; sVa[0] = s.va;
-        sKey[0] = level_key(hit, s.tk);
-      }
-    } else {
-#pragma unroll
-      for (int j = NS - 1; j > 0; --j) {
-        sDli[j] = sDli[j - 1]; sDi[j] = sDi[j - 1]; sSpec[j] = sSpec[j - 1]; sVa[j] = sVa[j - 1];
-        sKey[j] = sKey[j - 1];
-      }
-      sDli[0] = s.dli; sDi[0] = s.di; sSpec[0] = s.spec; sVa[0] = s.va;
-      sKey[0] = level_key(hit, s.tk);
-    }
-    if constexpr (!FWD) ++depth;
+    // the reflected ray becomes the next level (the level's colour is already in cr, cg, cb)
     reflect_dir(dx, dy, dz, s.nx, s.ny, s.nz);
     ox = s.qx;
     oy = s.qy;
@@ -2037,48 +1928,6 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
     if (st && !rin) stat_add(st, RTX_S_DEFERRED, 1);
     return;
   }
-  // fold back (shader.py:106-110): col_k = ((A_k + (spec_k + col_{k+1}*0.5) * g_k) + I_k); the
-  // stored levels were lit with g != 0
-  const double* mtab = (LDS ? (const double*)lds_tab : p.scene + RTX_HDR_WORDS) + nsph * RTX_GEOM_WORDS;
-  if constexpr (LV) {
-    if constexpr (NL < B) {
-      for (int d = depth - 1; d >= NL; --d) {  // the register levels first (the deepest)
-        const int key = sKey[0];
-        hit_color<IMG>(mtab + key_hit(key) * RTX_MAT_WORDS, sc, sDli[0], sDi[0], key_tex(key), true, true,
-                  sSpec[0], sVa[0], cr, cg, cb, cr, cg, cb);
-#pragma unroll
-        for (int j = 0; j < NR - 1; ++j) {
-          sDli[j] = sDli[j + 1]; sDi[j] = sDi[j + 1]; sSpec[j] = sSpec[j + 1]; sVa[j] = sVa[j + 1];
-          sKey[j] = sKey[j + 1];
-        }
-      }
-    }
-    for (int d = (depth < NL ? depth : NL) - 1; d >= 0; --d) {
-      const double* const l = lvd + (d * 4) * FB + lt;
-      const int key = lvk[d * FB + lt];
-      hit_color<IMG>(mtab + key_hit(key) * RTX_MAT_WORDS, sc, l[0], l[FB], key_tex(key), true, true,
-                l[2 * FB], l[3 * FB], cr, cg, cb, cr, cg, cb);
-    }
-  } else {
-    for (int d = 0; d < depth; ++d) {
-      const int key = sKey[0];
-      hit_color<IMG>(mtab + key_hit(key) * RTX_MAT_WORDS, sc, sDli[0], sDi[0], key_tex(key), true, true, sSpec[0],
-                sVa[0], cr, cg, cb, cr, cg, cb);
-#pragma unroll
-      for (int j = 0; j < NS - 1; ++j) {
-        sDli[j] = sDli[j + 1]; sDi[j] = sDi[j + 1]; sSpec[j] = sSpec[j + 1]; sVa[j] = sVa[j + 1];
-        sKey[j] = sKey[j + 1];
-      }
-    }
-  }
-  if constexpr (DEEP && !FWD) {  // a continued chain: fold on through the levels of its record (same fold)
-    for (int l = kb - 1; l >= 0; --l) {
-      const double* lv = rin + 6 + kRecLevelWords * l;
-      const int key = (int)lv[4];
-      hit_color<IMG>(mtab + key_hit(key) * RTX_MAT_WORDS, sc, lv[0], lv[1], key_tex(key), true, true, lv[2], lv[3],
-                cr, cg, cb, cr, cg, cb);
-    }
-  }
   write_out(p, io, cr, cg, cb);
 }
 
@@ -2087,18 +1936,16 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
 // DEEP: 0 capped (the chain ends at level B), 1 the first pass of an uncapped render (chains alive at
 // its record level are deferred with a resume record), 2 a continuation pass (mode 2: chains resumed
 // from their records; its own instantiation, so that the first pass compiles no resume code)
-template <int B, bool LDS, int DEEP, bool LVL, bool STATS, int TP, bool IMG, int NSPH>
+template <int B, bool LDS, int DEEP, bool STATS, int TP, bool IMG, int NSPH>
 __device__ __forceinline__ void k_render_fast_tiles(const Params& p, const double* lds_tab);
 
 // WAVES > 0: that many waves/SIMD instead of the rule below (kFwdWavesLarge)
-template <int B, bool LDS, int DEEP, bool LVL = levels_in_lds<B, LDS, (DEEP != 0)>(), bool STATS = false, int TP = 2,
-          bool IMG = false, int NSPH = 0, int WAVES = 0>
+template <int B, bool LDS, int DEEP, bool STATS = false, int TP = 2, bool IMG = false, int NSPH = 0, int WAVES = 0>
 __global__ __launch_bounds__(fast_block<(TP >= 1)>(),
                              WAVES > 0 ? WAVES
-                             : (DEEP  ? (TP >= 2 || DEEP == 2 ? kDeepWaves : kDeepWavesTile)
-                              : LVL ? (B >= 5 ? kB5Waves : TP ? kLvWaves : kLvWavesSmall)
-                              : kForwardFold ? (TP >= 2 ? kFwdWavesPersist : TP ? kFwdWaves : kFwdWavesSmall)
-                                             : kFastWavesPerSimd)) void k_render_fast(Params p0) {
+                             : DEEP    ? (TP >= 2 || DEEP == 2 ? kDeepWaves : kDeepWavesTile)
+                                       : (TP >= 2 ? kFwdWavesPersist : TP ? kFwdWaves : kFwdWavesSmall)) void
+k_render_fast(Params p0) {
   constexpr bool TREE = TP >= 1;
   // reflected-ray beams (wave_beam): the persistent launches, scenes of kPersistMinSpheres and more
   // (A/B: C4 -5.3%; with 16 spheres the tree walk is cheaper than the beam, C3 +7%, C5 +4%), capped
@@ -2129,15 +1976,15 @@ __global__ __launch_bounds__(fast_block<(TP >= 1)>(),
   if constexpr (DEEP == 2) {  // continuation pass (mode 2): 256 entries of in_list per tile, grid-stride
     const int64_t count = (int64_t)*p.in_count;
     for (int64_t t = blockIdx.x; t * fast_block<TREE>() < count; t += gridDim.x) {
-      fast_tile<B, LDS, DEEP, LVL, STATS, TREE, BEAM, IMG, NSPH>(p, (int)t, 0, t == (int64_t)blockIdx.x, lds_tab);
+      fast_tile<B, LDS, DEEP, STATS, TREE, BEAM, IMG, NSPH>(p, (int)t, 0, t == (int64_t)blockIdx.x, lds_tab);
     }
   } else {
-    k_render_fast_tiles<B, LDS, DEEP, LVL, STATS, TP, IMG, NSPH>(p, lds_tab);
+    k_render_fast_tiles<B, LDS, DEEP, STATS, TP, IMG, NSPH>(p, lds_tab);
   }
 }
 
 // the camera / explicit-ray launches of k_render_fast (every instantiation but the continuation's)
-template <int B, bool LDS, int DEEP, bool LVL, bool STATS, int TP, bool IMG, int NSPH>
+template <int B, bool LDS, int DEEP, bool STATS, int TP, bool IMG, int NSPH>
 __device__ __forceinline__ void k_render_fast_tiles(const Params& p, const double* lds_tab) {
   constexpr bool TREE = TP >= 1;
   constexpr bool BEAM = TP >= 2;
@@ -2178,7 +2025,7 @@ __device__ __forceinline__ void k_render_fast_tiles(const Params& p, const doubl
         // instantiations (run_render picks one for a launch that records them): in the timed kernel
         // the record costs C4 six more spilled VGPRs and 2.5% (A/B r4h)
         if (STATS && p.tile_cost && lane == 0) p.tile_cost[t] = 0u - (uint32_t)__builtin_amdgcn_s_memrealtime();
-        fast_tile<B, LDS, DEEP, LVL, STATS, TREE, BEAM, IMG, NSPH>(p, t - row * p.n_tiles_x, p.n_tiles_y - 1 - row, false,
+        fast_tile<B, LDS, DEEP, STATS, TREE, BEAM, IMG, NSPH>(p, t - row * p.n_tiles_x, p.n_tiles_y - 1 - row, false,
                                                               lds_tab, true);
         if (STATS && p.tile_cost && lane == 0) atomicAdd(p.tile_cost + t, (uint32_t)__builtin_amdgcn_s_memrealtime());
       }
@@ -2205,7 +2052,7 @@ __device__ __forceinline__ void k_render_fast_tiles(const Params& p, const doubl
     bx = tb % gridDim.x;
     by = gridDim.y - 1 - tb / gridDim.x;
   }
-  fast_tile<B, LDS, DEEP, LVL, STATS, TREE, BEAM, IMG, NSPH>(p, bx, by, true, lds_tab);
+  fast_tile<B, LDS, DEEP, STATS, TREE, BEAM, IMG, NSPH>(p, bx, by, true, lds_tab);
   if (STATS && p.tile_cost && (threadIdx.x & 63) == 0)  // the block's time: the slowest of its waves
     atomicMax(p.tile_cost + tb, (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_entry));
 }
@@ -2239,7 +2086,6 @@ __device__ void trace_general(const Params& p, const Stk& S, double ox0, double 
                               double dy0, double dz0, double& cr, double& cg, double& cb, int rays_through,
                               int hits_through, const double* rec = nullptr, int h_given = -1,
                               double t_given = 0.0) {
-  static_assert(kForwardFold, "the general kernel sums forwards, like the fast kernels");
   const cdouble* sc = (const cdouble*)p.scene;
   const cdouble* geo = sc + RTX_HDR_WORDS;
   const double* tab = p.scene + RTX_HDR_WORDS;
@@ -2394,7 +2240,7 @@ __global__ __launch_bounds__(64) void k_render_general(Params p0) {
           double cr, cg, cb;
           const bool given = q.mode == 3;
           trace_general(q, S, ox, oy, oz, dx, dy, dz, cr, cg, cb, rays_through, hits_through,
-                        resume ? p.in_rec + item * rec_words(p.in_level) : nullptr, given ? q.hit_shape : -1,
+                        resume ? p.in_rec + item * kRecWords : nullptr, given ? q.hit_shape : -1,
                         given ? q.hit_t[i] : 0.0);
           write_out(q, i, cr, cg, cb);
           todo = false;
@@ -2612,10 +2458,10 @@ __global__ __launch_bounds__(kBlock) void k_assemble_rows(const uint8_t* __restr
 // gains the small-scene kernels C2 -0.5..-0.9%, C1 -2.4% and costs the culled kernels C4 +1.4%
 // (profiles/r3_ab_variants.txt r3x-r3z).
 #ifndef RTX_DEVICE_CODE_ONLY
-// Launches k_render_fast<B, true, deep, lvl, stats, 0>(*params) on s (events e0/e1 as
+// Launches k_render_fast<B, true, deep, stats, 0, img>(*params) on s (events e0/e1 as
 // hipExtLaunchKernelGGL's); hipErrorInvalidValue, nothing launched, for an instantiation the unit
 // does not carry.
-__attribute__((visibility("hidden"))) hipError_t rtx_launch_small(int B, int deep, bool lvl, bool stats, bool img,
+__attribute__((visibility("hidden"))) hipError_t rtx_launch_small(int B, int deep, bool stats, bool img,
                                                                   const void* params, dim3 grid, uint32_t lds,
                                                                   hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 namespace {
@@ -2715,34 +2561,29 @@ int64_t workers_for(int64_t n, int max_bounces) {
 
 size_t list_bytes(int64_t n) { return (size_t)n * sizeof(int64_t); }
 
-// resume records of deferral pass `pass`: only when chains are deferred for depth
-int64_t records_for(int64_t n, int max_bounces, int pass = 0) {
+// resume records of the first pass or (cont) the continuation pass: only when chains are deferred for depth
+int64_t records_for(int64_t n, int max_bounces, bool cont = false) {
   const bool capped = max_bounces >= 0 && max_bounces <= kCappedMax;
-  return capped ? 0 : records_cap(n, pass);
+  return capped ? 0 : records_cap(n, cont);
 }
 
 size_t round256(size_t b) { return (b + 255) / 256 * 256; }
 
-// Workspace: header | tile counters | list 1 | (deep chains:) lists 2 and 3 | records of level
-// kDeepLevels, kDeepLevel2 and kDeepLevel3 | general-kernel stacks
+// Workspace: header | tile counters | list 1 | (deep chains:) the continuation pass's list | the
+// first pass's records | the continuation pass's records | general-kernel stacks
 struct WsLayout {
-  size_t fetch, list1, list2, list3, rec1, rec2, rec3, stack, total;
+  size_t fetch, list1, cont_list, rec1, cont_rec, stack, total;
 };
 WsLayout ws_layout(int64_t n, int max_bounces) {
   WsLayout w{};
   const int64_t nrec = records_for(n, max_bounces);
-  const int64_t nrec2 = records_for(n, max_bounces, 1);
-  const int64_t nrec3 = records_for(n, max_bounces, 2);
+  const int64_t ncont = records_for(n, max_bounces, true);
   w.fetch = RTX_WS_HDR_BYTES;
   w.list1 = w.fetch + (size_t)kMaxFetch * kFetchStride * sizeof(uint32_t);
-  // (forward fold: the first continuation pass, list 2 and its records, is never launched — run_render
-  // starts at the second — so they take no bytes; ADVICE r5: 275 MB of the unbounded C4 workspace)
-  w.list2 = w.list1 + round256(list_bytes(n));
-  w.list3 = w.list2 + (nrec && !kForwardFold ? round256(list_bytes(n)) : 0);
-  w.rec1 = w.list3 + (nrec ? round256(list_bytes(n)) : 0);
-  w.rec2 = w.rec1 + round256((size_t)nrec * rec_words(kDeepLevels) * sizeof(double));
-  w.rec3 = w.rec2 + (kForwardFold ? 0 : round256((size_t)nrec2 * rec_words(kDeepLevel2) * sizeof(double)));
-  w.stack = w.rec3 + round256((size_t)nrec3 * rec_words(kDeepLevel3) * sizeof(double));
+  w.cont_list = w.list1 + round256(list_bytes(n));
+  w.rec1 = w.cont_list + (nrec ? round256(list_bytes(n)) : 0);
+  w.cont_rec = w.rec1 + round256((size_t)nrec * kRecWords * sizeof(double));
+  w.stack = w.cont_rec + round256((size_t)ncont * kRecWords * sizeof(double));
   w.total = w.stack + (size_t)workers_for(n, max_bounces) * stack_levels_for(max_bounces) * kFrameWords * 8;
   return w;
 }
@@ -2750,7 +2591,7 @@ WsLayout ws_layout(int64_t n, int max_bounces) {
 size_t ws_bytes(int64_t n, int max_bounces) { return ws_layout(n, max_bounces).total; }
 
 // The block-tile grid of a camera launch that is not persistent: the TREE = false kernels (scenes below
-// kTreeMinSpheres, launch_fast_lds_s) use wave_w<false>() pixels per wave row.
+// kTreeMinSpheres, launch_fast_lds) use wave_w<false>() pixels per wave row.
 void block_grid(int nsph, int width, int n_rows, int64_t& gx, int64_t& gy) {
   const bool small = nsph < kTreeMinSpheres;
   const int wx = small ? waves_x<false>() : waves_x<true>();
@@ -2788,71 +2629,49 @@ dim3 persistent_grid(K kernel, size_t lds, Params& p) {
 // Launches that are not persistent run instantiations without the persistent tile loop (TP 1), and
 // scenes below kTreeMinSpheres, which carry no culling tree (scene_pack.BVH_MIN_SPHERES), ones
 // without the tree walks either (TP 0) (A/B in DESIGN.md §4).
-template <int B, int DEEP, bool LVL, bool STATS, bool IMG = false>
-void launch_fast_lds_s(Params& p, dim3 grid, hipStream_t s) {
+template <int B, int DEEP, bool STATS, bool IMG = false>
+void launch_fast_lds(Params& p, dim3 grid, hipStream_t s) {
   const bool small = p.nsph < kTreeMinSpheres;  // the TREE = false kernels: fast_block<false>() threads
   const size_t lds = (size_t)p.nsph * kSphWords * sizeof(double) +
-                     (LVL ? (small ? level_lds_bytes<(DEEP != 0), false>(B) : level_lds_bytes<(DEEP != 0)>(B)) : 0) +
-                     (kForwardFold && !DEEP && !small && p.n_fetch == 0 ? kColourLdsBytes : 0);  // TP 1
+                     (!DEEP && !small && p.n_fetch == 0 ? kColourLdsBytes : 0);  // TP 1
   if (p.n_fetch == 0) {  // one tile per block: the instantiations without the persistent loop
     if (p.nsph < kTreeMinSpheres) {  // TP 0: the rtx_small.hip unit
       const hipError_t e =
-          rtx_launch_small(B, DEEP, LVL, STATS, IMG, &p, grid, (uint32_t)lds, s, prof_event(0), prof_event(1));
+          rtx_launch_small(B, DEEP, STATS, IMG, &p, grid, (uint32_t)lds, s, prof_event(0), prof_event(1));
       if (e != hipSuccess) g_small_err = e;
     } else {
-      if constexpr (!DEEP && !STATS && !IMG && kForwardFold) {
+      if constexpr (!DEEP && !STATS && !IMG) {
         if ((int64_t)p.n * p.n_frames >= kWavesLargeMinPixels) {  // a large launch: more waves (kFwdWavesLarge)
-          hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, LVL, STATS, 1, IMG, 0, kFwdWavesLarge>), grid,
+          hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, STATS, 1, IMG, 0, kFwdWavesLarge>), grid,
                                 dim3(kFastBlock), (uint32_t)lds, s, prof_event(0), prof_event(1), 0u, p);
           return;
         }
       }
-      hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, LVL, STATS, 1, IMG>), grid, dim3(kFastBlock), (uint32_t)lds,
-                            s, prof_event(0), prof_event(1), 0u, p);
+      hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, STATS, 1, IMG>), grid, dim3(kFastBlock), (uint32_t)lds, s,
+                            prof_event(0), prof_event(1), 0u, p);
     }
     return;
   }
-  if (p.n_fetch > 0) grid = persistent_grid(k_render_fast<B, true, DEEP, LVL, STATS, 2, IMG>, lds, p);
-  hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, LVL, STATS, 2, IMG>), grid, dim3(kFastBlock), (uint32_t)lds, s,
+  if (p.n_fetch > 0) grid = persistent_grid(k_render_fast<B, true, DEEP, STATS, 2, IMG>, lds, p);
+  hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, STATS, 2, IMG>), grid, dim3(kFastBlock), (uint32_t)lds, s,
                         prof_event(0), prof_event(1), 0u, p);
-}
-template <int B, int DEEP, bool LVL>
-void launch_fast_lds(Params& p, dim3 grid, hipStream_t s) {
-  if (p.stats || p.tile_cost) {  // (the cost records of a learning launch live in the STATS kernels)
-    launch_fast_lds_s<B, DEEP, LVL, true>(p, grid, s);
-  } else if (!DEEP && p.images) {  // image textures shaded in place (capped renders only)
-    launch_fast_lds_s<B, DEEP, LVL, false, !DEEP>(p, grid, s);
-  } else {
-    launch_fast_lds_s<B, DEEP, LVL, false>(p, grid, s);
-  }
 }
 
 template <int B, int DEEP = 0>
 void launch_fast_b(const Params& p0, dim3 grid, hipStream_t s) {
   Params p = p0;
   if (p.nsph <= kLdsMaxSpheres) {
-    if constexpr (DEEP) {
-      // (forward fold: no level slots, so no LDS for them and the occupancy the registers allow)
-      if (!kForwardFold && kLevelsInLds && p.nsph <= kDeepLvMaxSpheres) {
-        launch_fast_lds<B, DEEP, true>(p, grid, s);
-      } else {
-        launch_fast_lds<B, DEEP, false>(p, grid, s);
-      }
+    if (p.stats || p.tile_cost) {  // (the cost records of a learning launch live in the STATS kernels)
+      launch_fast_lds<B, DEEP, true>(p, grid, s);
+    } else if (!DEEP && p.images) {  // image textures shaded in place (capped renders only)
+      launch_fast_lds<B, DEEP, false, !DEEP>(p, grid, s);
     } else {
-      // caps 3-4 in big scenes: three LDS level slots beside a large scene table leave room for
-      // fewer than 4 blocks per CU; the register-level kernel (128 VGPRs, 4 waves/SIMD) then runs
-      // more waves than the LDS-slot kernel can
-      constexpr bool kTry = B == 3 || B == 4;
-      if (kTry && (size_t)p.nsph * kSphWords * sizeof(double) + level_lds_bytes(B) > kLdsBytesPerCu / 4) {
-        if constexpr (kTry) launch_fast_lds<B, false, false>(p, grid, s);
-      } else {
-        launch_fast_lds<B, false, levels_in_lds<B, true, false>()>(p, grid, s);
-      }
+      launch_fast_lds<B, DEEP, false>(p, grid, s);
     }
   } else {
     if (p.stats || p.tile_cost) {
-      if (p.n_fetch > 0) grid = persistent_grid(k_render_fast<B, false, DEEP, false, true>, 0, p);
-      hipExtLaunchKernelGGL((k_render_fast<B, false, DEEP, false, true>), grid, dim3(kFastBlock), 0u, s,
+      if (p.n_fetch > 0) grid = persistent_grid(k_render_fast<B, false, DEEP, true>, 0, p);
+      hipExtLaunchKernelGGL((k_render_fast<B, false, DEEP, true>), grid, dim3(kFastBlock), 0u, s,
                             prof_event(0), prof_event(1), 0u, p);
     } else {
       if (p.n_fetch > 0) grid = persistent_grid(k_render_fast<B, false, DEEP>, 0, p);
@@ -2864,7 +2683,7 @@ void launch_fast_b(const Params& p0, dim3 grid, hipStream_t s) {
 
 // caps above kCappedMax or none: kDeepLevels levels, longer chains deferred with a record
 void launch_fast_deep(const Params& p, dim3 grid, hipStream_t s) { launch_fast_b<kDeepLevels, 1>(p, grid, s); }
-// ... and their continuation passes (mode 2)
+// ... and their continuation pass (mode 2)
 void launch_fast_cont(const Params& p, dim3 grid, hipStream_t s) { launch_fast_b<kDeepLevels, 2>(p, grid, s); }
 
 void launch_fast(int B, const Params& p, dim3 grid, hipStream_t s) {
@@ -2900,9 +2719,7 @@ int run_render(Params& p, void* workspace, size_t workspace_bytes, hipStream_t s
   const WsLayout lay = ws_layout(n_all, p.max_bounces);
   uint32_t* const hdr = (uint32_t*)p.ws;
   uint64_t* const list1 = (uint64_t*)(p.ws + lay.list1);
-  uint64_t* const list2 = (uint64_t*)(p.ws + lay.list2);
   double* const rec1 = (double*)(p.ws + lay.rec1);
-  double* const rec2 = (double*)(p.ws + lay.rec2);
   p.rec_cap = records_for(n_all, p.max_bounces);
   p.in_rec_cap = p.rec_cap;
   p.stack = (double*)(p.ws + lay.stack);
@@ -2931,7 +2748,7 @@ int run_render(Params& p, void* workspace, size_t workspace_bytes, hipStream_t s
     p.dlist = list1;
     p.dcount = hdr + RTX_WS_COUNT;
     p.drec = capped ? nullptr : rec1;
-    p.drec_level = kForwardFold ? kFirstPassLevels : kDeepLevels;
+    p.drec_level = kFirstPassLevels;
     prof_mark(0, s);
     if (capped) {
       launch_fast(p.max_bounces, p, grid, s);
@@ -2945,39 +2762,30 @@ int run_render(Params& p, void* workspace, size_t workspace_bytes, hipStream_t s
   p.in_list = list1;
   p.in_count = hdr + RTX_WS_COUNT;
   p.in_rec = capped ? nullptr : rec1;
-  p.in_level = kForwardFold ? kFirstPassLevels : kDeepLevels;
+  p.in_level = kFirstPassLevels;
   if (!capped && p.n_frames == 1 && !no_general) {
-    // continuation passes: chains deferred for depth go on for kDeepLevels + 1 more levels in
-    // the register-resident kernel, twice; ties and what is still alive after them go to the
+    // the continuation pass: chains deferred for depth go on from level kFirstPassLevels + 1 to
+    // kDeepLevel3 in the register-resident kernel; ties and what is still alive after it go to the
     // general kernel
-    uint64_t* const lists[2] = {list2, (uint64_t*)(p.ws + lay.list3)};
-    uint32_t* const counts[2] = {hdr + RTX_WS_COUNT2, hdr + RTX_WS_COUNT3};
-    double* const recs[2] = {rec2, (double*)(p.ws + lay.rec3)};
-    const int levels[2] = {kDeepLevel2, kDeepLevel3};
-    const int64_t caps[2] = {records_for(n_all, p.max_bounces, 1), records_for(n_all, p.max_bounces, 2)};
-    // (forward fold: one continuation pass goes on from level kDeepLevels + 1 to kDeepLevel3)
-    for (int pass = kForwardFold ? 1 : 0; pass < 2; ++pass) {
-      Params q = p;
-      q.mode = 2;
-      q.n_tiles_x = q.n_tiles_y = 0;
-      q.n_fetch = 0;
-      q.dlist = lists[pass];
-      q.dcount = counts[pass];
-      q.drec = recs[pass];
-      q.drec_level = levels[pass];
-      q.rec_cap = caps[pass];
-      q.in_rec_cap = p.in_rec_cap;
-      const int64_t fb = p.nsph < kTreeMinSpheres ? fast_block<false>() : fast_block<true>();
-      const int64_t tiles = (n_all + fb - 1) / fb;
-      const int64_t cap = 4 * (int64_t)device_cus();
-      launch_fast_cont(q, dim3((unsigned)(tiles < cap ? tiles : cap)), s);
-      if (int e = check_launch("k_render_fast (continuation)")) return e;
-      p.in_list = lists[pass];
-      p.in_count = counts[pass];
-      p.in_rec = recs[pass];
-      p.in_level = levels[pass];
-      p.in_rec_cap = caps[pass];
-    }
+    Params q = p;
+    q.mode = 2;
+    q.n_tiles_x = q.n_tiles_y = 0;
+    q.n_fetch = 0;
+    q.dlist = (uint64_t*)(p.ws + lay.cont_list);
+    q.dcount = hdr + RTX_WS_COUNT3;
+    q.drec = (double*)(p.ws + lay.cont_rec);
+    q.drec_level = kDeepLevel3;
+    q.rec_cap = records_for(n_all, p.max_bounces, true);
+    const int64_t fb = p.nsph < kTreeMinSpheres ? fast_block<false>() : fast_block<true>();
+    const int64_t tiles = (n_all + fb - 1) / fb;
+    const int64_t cap = 4 * (int64_t)device_cus();
+    launch_fast_cont(q, dim3((unsigned)(tiles < cap ? tiles : cap)), s);
+    if (int e = check_launch("k_render_fast (continuation)")) return e;
+    p.in_list = q.dlist;
+    p.in_count = q.dcount;
+    p.in_rec = q.drec;
+    p.in_level = q.drec_level;
+    p.in_rec_cap = q.rec_cap;
   }
   // deferred rays: ties, and chains longer than the fast kernel's levels
   if (no_general) return RTX_OK;  // (an uncapped render: nor the continuation pass)

@@ -593,8 +593,9 @@ def test_rays_at_right_angles_take_reference_expressions(hip):
 
 @pytest.mark.parametrize("B", [3, 4])
 def test_big_scene_register_level_kernel(hip, B):
-    """65 spheres at caps 3 and 4: the LDS-slot kernel would fit 3 blocks per CU beside the scene
-    table, so the register-level kernel renders it (launch_fast_b); colour, uint8 and counters."""
+    """65 spheres at caps 3 and 4, a big scene table in LDS beside a mid-size cap (the name dates from
+    a choice between two kernels that launch_fast_b no longer makes: every cap has one capped
+    kernel); colour, uint8 and counters."""
     spec = scenes.random_spec(64, 3, 96, 54)
     r, got = _render(hip, spec, B, stats=True)
     st = O.TraceStats()

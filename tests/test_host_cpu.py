@@ -96,6 +96,28 @@ def test_workspace_bytes_and_error_paths():
     assert lib.rtx_sphere_intersect(None, None, 0, None, 5, None, None) == -1
 
 
+def test_workspace_bytes_pinned():
+    """rtx_workspace_bytes is public behaviour (callers size and keep buffers by it): the values below
+    were recorded from a build of commit 896f684, before the workspace layout was rewritten for the
+    single continuation pass. The pixel counts cross every branch of the resume-record capacities
+    (fewer pixels than records wanted, the 2^18 floor, the one-per-32-pixels slope) and of the
+    general kernel's worker count (bound by the pixels, by the capped and the deep worker limits,
+    and by the stack budget of an unbounded render)."""
+    caps = (0, 3, 6, 7, -1)
+    recorded = {
+        1: (14848, 45568, 76288, 87296, 3415296),
+        576: (101120, 377600, 654080, 843008, 30795008),
+        23400: (847104, 2813184, 4779264, 24533504, 538919424),
+        2073600: (17248512, 19214592, 21180672, 76435712, 590821632),
+        33177600: (266080512, 268046592, 270012672, 636072192, 1150458112),
+        66355200: (531501312, 533467392, 535433472, 1251139072, 1765524992),
+    }
+    lib = L.load()
+    for n, want in recorded.items():
+        got = tuple(lib.rtx_workspace_bytes(n, cap) for cap in caps)
+        assert got == want, (n, got, want)
+
+
 def test_sched_and_tiles_entry_points_validate_on_host():
     """The dispatch-order and row-tiled-frame entry points (round 4): unit counts of a launch, and
     the argument checks that run before any HIP or RCCL call (no GPU needed)."""

@@ -40,7 +40,7 @@ def trim(src: str, caps: set) -> str:
         sub("    default: launch_fast_b<6>(p, grid, s); break;", "    default: break;")
     sub("{ launch_fast_b<kDeepLevels, 1>(p, grid, s); }", "{}")
     sub("{ launch_fast_b<kDeepLevels, 2>(p, grid, s); }", "{}")
-    sub("    launch_fast_lds_s<B, DEEP, LVL, true>(p, grid, s);", "    launch_fast_lds_s<B, DEEP, LVL, false>(p, grid, s);")
+    sub("      launch_fast_lds<B, DEEP, true>(p, grid, s);", "      launch_fast_lds<B, DEEP, false>(p, grid, s);")
     return src
 
 

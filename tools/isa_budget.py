@@ -2,7 +2,10 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -disable-machine-licm \
           -gline-tables-only --cuda-device-only -S -o rtx.s python_ray_tracer_amd/csrc/rtx_kernels.hip
-    python tools/isa_budget.py rtx.s '_ZN12_GLOBAL__N_113k_render_fastILi3ELb1ELb0ELb1ELb0EEEvNS_6ParamsE'
+    python tools/isa_budget.py rtx.s '_ZN12_GLOBAL__N_113k_render_fastILi3ELb1ELi0ELb0ELi2ELb0ELi0ELi0EEEvNS_6ParamsE'
+
+(the second argument names a kernel: here k_render_fast<B = 3, LDS, DEEP 0, STATS = false, TP 2, IMG =
+false, NSPH 0, WAVES 0>, the persistent capped kernel of cap 3)
 
 Every instruction is attributed to the innermost source line of its `.loc` (inlined helpers keep
 their own lines) and that line to the enclosing function of rtx_kernels.hip; instructions are
