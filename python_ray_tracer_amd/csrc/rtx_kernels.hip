@@ -555,6 +555,48 @@ __device__ __forceinline__ bool shadows(bool valid, double t, double tself, bool
   return valid ? t < tself : far_self;
 }
 
+// Records first .. end - 1 of a geometry table (the scene's, or the culled list), wave-uniform, two
+// at a time through isect_pair and an odd one left through isect_one: disc(g) starts a record's test,
+// sph(g, k) names its sphere, use(s, root, valid) consumes it, record k before k + 1 (the tie flag
+// depends on scene order). readfirstlane keeps k scalar in divergent loops. Callers count their work.
+template <typename P, typename Disc, typename Sph, typename Use>
+__device__ __forceinline__ void scan_range(const P* geo, int first, int end, Disc&& disc, Sph&& sph, Use&& use) {
+  int k = first;
+  for (; k + 1 < end; k += 2) {
+    const P* g0 = geo + __builtin_amdgcn_readfirstlane(k) * RTX_GEOM_WORDS;
+    const P* g1 = g0 + RTX_GEOM_WORDS;
+    const SphTest a0 = disc(g0), a1 = disc(g1);
+    const int s0 = sph(g0, k), s1 = sph(g1, k + 1);
+    isect_pair(a0, a1, [&](double t0, bool v0, double t1, bool v1) {
+      use(s0, t0, v0);
+      use(s1, t1, v1);
+    });
+  }
+  if (k < end) {
+    const P* g0 = geo + __builtin_amdgcn_readfirstlane(k) * RTX_GEOM_WORDS;
+    const SphTest a0 = disc(g0);
+    const int s0 = sph(g0, k);
+    isect_one(a0, [&](double t0, bool v0) { use(s0, t0, v0); });
+  }
+}
+
+// Stackless depth-first walk of the culling tree: a node is entered when may(node) holds in any lane,
+// else its subtree is skipped (RTX_N_SKIP). leaf(first, cnt) takes an entered node's range of the
+// culled list (cnt == 0: an inner node) and returns whether to go on (wave-uniform).
+template <typename May, typename Leaf>
+__device__ __forceinline__ void tree_walk(const cdouble* nodes, int nn, May&& may, Leaf&& leaf) {
+  int i = 0;
+  while (i < nn) {
+    const cdouble* nd = nodes + __builtin_amdgcn_readfirstlane(i) * RTX_NODE_WORDS;
+    if (__ballot(may(nd)) != 0) {
+      if (!leaf((int)nd[RTX_N_FIRST], (int)nd[RTX_N_COUNT])) break;
+      ++i;
+    } else {
+      i = (int)nd[RTX_N_SKIP];
+    }
+  }
+}
+
 // ---- culling hierarchy ---------------------------------------------------------------------
 // Conservative test: may any sphere inside a node's box produce, through the reference formula
 // (shape.py:34-51), a hit with 0 < t <= tlim? If this returns false, every such sphere provably
@@ -593,38 +635,23 @@ __device__ __forceinline__ bool node_may_hit(const cdouble* nd, double ox, doubl
   return tn <= tf && tf >= 0.0 && tn <= tlim;
 }
 
-// Nearest hit over entries [first, first + cnt) of the culled geometry list (pairs, scalar loads).
+// Nearest hit over entries [first, first + cnt) of the culled geometry list.
 template <bool CAM, typename Wk>
 __device__ __forceinline__ void nearest_range(const cdouble* cg, int first, int cnt, double ox, double oy, double oz,
                                               double oo, double dx, double dy, double dz, double& tmin, int& hit,
                                               bool& tie, double tame, Wk& wk) {
   wk.test(cnt);
-  const int end = first + cnt;
-  int k = first;
-  for (; k + 1 < end; k += 2) {
-    const cdouble* g0 = cg + __builtin_amdgcn_readfirstlane(k) * RTX_GEOM_WORDS;
-    const cdouble* g1 = g0 + RTX_GEOM_WORDS;
-    const SphTest a0 = CAM ? isect_disc_cam(g0, ox, oy, oz, dx, dy, dz, tame)
-                           : isect_disc(g0, ox, oy, oz, oo, dx, dy, dz, tame);
-    const SphTest a1 = CAM ? isect_disc_cam(g1, ox, oy, oz, dx, dy, dz, tame)
-                           : isect_disc(g1, ox, oy, oz, oo, dx, dy, dz, tame);
-    const int s0 = (int)g0[RTX_G_IDX], s1 = (int)g1[RTX_G_IDX];
-    isect_pair(a0, a1, [&](double t0, bool v0, double t1, bool v1) {
-      nearest_update(v0, t0, s0, tmin, hit, tie);
-      nearest_update(v1, t1, s1, tmin, hit, tie);
-    });
-  }
-  if (k < end) {
-    const cdouble* g0 = cg + __builtin_amdgcn_readfirstlane(k) * RTX_GEOM_WORDS;
-    const SphTest a0 = CAM ? isect_disc_cam(g0, ox, oy, oz, dx, dy, dz, tame)
-                           : isect_disc(g0, ox, oy, oz, oo, dx, dy, dz, tame);
-    const int s0 = (int)g0[RTX_G_IDX];
-    isect_one(a0, [&](double t0, bool v0) { nearest_update(v0, t0, s0, tmin, hit, tie); });
-  }
+  scan_range(
+      cg, first, first + cnt,
+      [&](const cdouble* g) {
+        return CAM ? isect_disc_cam(g, ox, oy, oz, dx, dy, dz, tame) : isect_disc(g, ox, oy, oz, oo, dx, dy, dz, tame);
+      },
+      [](const cdouble* g, int) { return (int)g[RTX_G_IDX]; },
+      [&](int s, double t, bool v) { nearest_update(v, t, s, tmin, hit, tie); });
 }
 
-// Nearest hit through the culling tree: the always-tested spheres, then a stackless depth-first
-// walk that enters a node when any lane of the wave may hit it before its current nearest t.
+// Nearest hit through the culling tree: the always-tested spheres, then the walk, entering a node
+// when any lane of the wave may hit it before its current nearest t.
 // Evaluation order differs from scene order, which the result does not depend on: the nearest t
 // is a minimum, `hit` is its unique owner unless tied, and a tie is flagged whatever the order.
 template <bool CAM, typename Wk>
@@ -639,20 +666,17 @@ __device__ __forceinline__ void nearest_bvh(const cdouble* sc, double ox, double
   tie = false;
   nearest_range<CAM>(cg, 0, (int)sc[RTX_H_NALWAYS], ox, oy, oz, oo, dx, dy, dz, tmin, hit, tie, tame, wk);
   const RaySlab rs = ray_slab(dx, dy, dz, oo);
-  int i = 0;
-  while (i < nn) {
-    const cdouble* nd = nodes + __builtin_amdgcn_readfirstlane(i) * RTX_NODE_WORDS;
-    wk.node();
-    wk.box();
-    if (__ballot(node_may_hit(nd, ox, oy, oz, rs, tmin)) != 0) {
-      const int cnt = (int)nd[RTX_N_COUNT];
-      if (cnt > 0)
-        nearest_range<CAM>(cg, (int)nd[RTX_N_FIRST], cnt, ox, oy, oz, oo, dx, dy, dz, tmin, hit, tie, tame, wk);
-      ++i;
-    } else {
-      i = (int)nd[RTX_N_SKIP];
-    }
-  }
+  tree_walk(
+      nodes, nn,
+      [&](const cdouble* nd) {
+        wk.node();
+        wk.box();
+        return node_may_hit(nd, ox, oy, oz, rs, tmin);
+      },
+      [&](int first, int cnt) {
+        if (cnt > 0) nearest_range<CAM>(cg, first, cnt, ox, oy, oz, oo, dx, dy, dz, tmin, hit, tie, tame, wk);
+        return true;
+      });
 }
 
 // The general kernel's nearest pass through the culling tree: the nearest distance, how many
@@ -686,23 +710,20 @@ __device__ __forceinline__ void nearest_count_bvh(const cdouble* sc, double ox, 
   };
   range(0, (int)sc[RTX_H_NALWAYS]);
   const RaySlab rs = ray_slab(dx, dy, dz, oo);
-  int i = 0;
-  while (i < nn) {
-    const cdouble* nd = nodes + __builtin_amdgcn_readfirstlane(i) * RTX_NODE_WORDS;
-    if (__ballot(node_may_hit(nd, ox, oy, oz, rs, tmin)) != 0) {
-      const int cnt = (int)nd[RTX_N_COUNT];
-      if (cnt > 0) range((int)nd[RTX_N_FIRST], (int)nd[RTX_N_FIRST] + cnt);
-      ++i;
-    } else {
-      i = (int)nd[RTX_N_SKIP];
-    }
-  }
+  tree_walk(
+      nodes, nn, [&](const cdouble* nd) { return node_may_hit(nd, ox, oy, oz, rs, tmin); },
+      [&](int f, int cnt) {
+        if (cnt > 0) range(f, f + cnt);
+        return true;
+      });
 }
 
 // Shadow any-hit through the culling tree (shader.py:126-128 in its any-hit form): lit stays true
 // unless some sphere is strictly nearer than the shape itself along the light direction. hs: the
 // wave-uniform shape of every lane (nsph when the lanes differ), whose own test cannot shadow it.
 // Callers guarantee t_self <= FARAWAY in every lane (an invalid test then never shadows).
+// (Written out: through tree_walk and scan_range 43 rows of tools/resource_usage.py move, <6,1,0,0,1,1,0,0>
+// from 0 to 3 spilled VGPRs; so do the three mask loops, nearest_masked, nearest_beam and min_masked.)
 template <typename Wk>
 __device__ __forceinline__ bool lit_bvh(const cdouble* sc, double qx, double qy, double qz, double qq, double lx,
                                         double ly, double lz, double tself, int hs, double tame, Wk& wk) {
@@ -755,7 +776,7 @@ __device__ __forceinline__ bool lit_bvh(const cdouble* sc, double qx, double qy,
   return lit;
 }
 
-// Nearest hit of ray (O, D) over all spheres; wave-uniform loop over sphere pairs, geometry through
+// Nearest hit of ray (O, D) over all spheres, geometry through
 // the scalar cache. CAM: O is the camera (level 0), using the host-precomputed c.
 template <bool CAM, typename P, typename Wk>
 __device__ __forceinline__ void nearest_hit(const P* geo, int nsph, double ox, double oy, double oz, double dx,
@@ -766,25 +787,12 @@ __device__ __forceinline__ void nearest_hit(const P* geo, int nsph, double ox, d
   hit = -1;
   tie = false;
   const double oo = CAM ? 0.0 : dot3(ox, oy, oz, ox, oy, oz);
-  int s = 0;
-  for (; s + 1 < nsph; s += 2) {
-    const P* g0 = geo + __builtin_amdgcn_readfirstlane(s) * RTX_GEOM_WORDS;
-    const P* g1 = g0 + RTX_GEOM_WORDS;
-    const SphTest a0 = CAM ? isect_disc_cam(g0, ox, oy, oz, dx, dy, dz, tame)
-                           : isect_disc(g0, ox, oy, oz, oo, dx, dy, dz, tame);
-    const SphTest a1 = CAM ? isect_disc_cam(g1, ox, oy, oz, dx, dy, dz, tame)
-                           : isect_disc(g1, ox, oy, oz, oo, dx, dy, dz, tame);
-    isect_pair(a0, a1, [&](double t0, bool v0, double t1, bool v1) {
-      nearest_update(v0, t0, s, tmin, hit, tie);
-      nearest_update(v1, t1, s + 1, tmin, hit, tie);
-    });
-  }
-  if (s < nsph) {
-    const P* g0 = geo + __builtin_amdgcn_readfirstlane(s) * RTX_GEOM_WORDS;
-    const SphTest a0 = CAM ? isect_disc_cam(g0, ox, oy, oz, dx, dy, dz, tame)
-                           : isect_disc(g0, ox, oy, oz, oo, dx, dy, dz, tame);
-    isect_one(a0, [&](double t0, bool v0) { nearest_update(v0, t0, s, tmin, hit, tie); });
-  }
+  scan_range(
+      geo, 0, nsph,
+      [&](const P* g) {
+        return CAM ? isect_disc_cam(g, ox, oy, oz, dx, dy, dz, tame) : isect_disc(g, ox, oy, oz, oo, dx, dy, dz, tame);
+      },
+      [](const P*, int s) { return s; }, [&](int s, double t, bool v) { nearest_update(v, t, s, tmin, hit, tie); });
 }
 
 // (x)^5 and (x)^2.5 for x in [0, 1] (shader.py:291, :310). NumPy evaluates these with its SIMD pow;
@@ -961,7 +969,6 @@ __device__ __forceinline__ double specular(const M* mh, double g, double nx, dou
   const double sf = __builtin_fma(g, glint, spec_base);  // :315
   return (NdotV <= 0.0) ? 0.0 : sf;  // :318
 }
-
 
 // Colour of one shaded hit given the reflected colour R (shader.py:86-110):
 //   ((((0.004 + diffuse) + dome) + (spec + R*0.5)*g*lit) + irid)
@@ -1160,7 +1167,7 @@ __device__ __forceinline__ void shade(const cdouble* sc, const G* geo, const T* 
     double tsh = FARAWAY;
     bool anyv = false;
     int j = 0;
-    for (; j + 1 < nshadow; j += 2) {  // sphere pairs (one scalar-load wait, two interleaved chains)
+    for (; j + 1 < nshadow; j += 2) {  // (written out, not scan_range: the skip-hs remap takes both indices)
       const G* g0 = geo + __builtin_amdgcn_readfirstlane(j + (j >= hs)) * RTX_GEOM_WORDS;
       const G* g1 = geo + __builtin_amdgcn_readfirstlane(j + 1 + (j + 1 >= hs)) * RTX_GEOM_WORDS;
       wk.test(2);
@@ -1195,7 +1202,7 @@ __device__ __forceinline__ void shade(const cdouble* sc, const G* geo, const T* 
     if (culled) lit = lit_bvh(sc, qx, qy, qz, qq, lx, ly, lz, tself, hs, tame, wk);
     const int nshadow = culled ? 0 : nsph - (hs < nsph);
     int j = 0;
-    for (; j + 1 < nshadow; j += 2) {  // sphere pairs (one scalar-load wait, two interleaved chains)
+    for (; j + 1 < nshadow; j += 2) {  // (written out: the remap as above, and a lane leaves at its first shadow)
       const int j0 = __builtin_amdgcn_readfirstlane(j + (j >= hs));
       const int j1 = __builtin_amdgcn_readfirstlane(j + 1 + (j + 1 >= hs));
       const G* g0 = geo + j0 * RTX_GEOM_WORDS;
@@ -1895,8 +1902,6 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
       } else {
         nearest_bvh<false>(sc, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
       }
-    } else if constexpr (LDS) {
-      nearest_hit<false>(geo, nsph, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
     } else {
       nearest_hit<false>(geo, nsph, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
     }

@@ -840,3 +840,56 @@ def test_small_scene_with_a_tree_renders_without_it(hip, B):
     assert np.abs(got - want).max() <= ATOL
     _, plain = _render(hip, spec, B)
     assert np.array_equal(got, plain)
+
+
+@pytest.mark.parametrize("cap", [2, None])
+@pytest.mark.parametrize("n", range(9))
+def test_sphere_loop_tails_one_to_nine_spheres(hip, n, cap):
+    """1 to 9 spheres (n random ones and the ground): the odd and even tails of every sphere-pair
+    scan, each compile-time sphere count of the small-scene kernels (1..7) and both sides of
+    kTreeMinSpheres. The counting kernels against the oracle (colour, uint8, per-level rays and
+    hits), then three renders on one timed renderer (the third runs with the learnt dispatch order
+    and the decided general-kernel flag), bit-identical to each other and within ATOL of the
+    oracle."""
+    spec = scenes.random_spec(n, n, 32, 16)
+    st = O.TraceStats()
+    want = O.render(O.scene_from_spec(spec), cap, stats=st)
+    r, got = _render(hip, spec, cap, stats=True)
+    assert np.abs(got - want).max() <= ATOL, np.abs(got - want).max()
+    assert np.array_equal(O.to_uint8(got, 32, 16), O.to_uint8(want, 32, 16))
+    s = r.stats()
+    assert s["rays"] == st.rays and s["hits"] == st.hits
+    r2 = hip.HipRenderer(max_bounces=cap, color_dtype=torch.float64)
+    scene = scenes.build_scene(spec)
+    frames = [r2.render_tile(scene).cpu().numpy() for _ in range(3)]
+    assert np.array_equal(frames[0], frames[1]) and np.array_equal(frames[0], frames[2])
+    timed = frames[2].reshape(want.shape)
+    assert np.abs(timed - want).max() <= ATOL, np.abs(timed - want).max()
+    assert np.array_equal(O.to_uint8(timed, 32, 16), O.to_uint8(want, 32, 16))
+
+
+WORK_COUNTERS = ("sphere_tests", "node_tests", "sphere_tests_reflected", "node_tests_reflected", "box_tests",
+                 "beam_tests", "beam_searches")
+WORK_SCENES = {
+    "rand2_32x16": lambda: scenes.random_spec(2, 0, 32, 16),            # no culling tree
+    "rand15_48x27": lambda: scenes.random_spec(15, 1, 48, 27),          # a tree, one tile per block
+    "rand39_64x36": lambda: scenes.random_spec(39, 2, 64, 36),          # persistent: beams, shadow grid
+    "tail_below_64_80x45": lambda: huge_tail_spec("tail_below_64", 80, 45),
+}
+
+
+def work_counters(H, name, cap):
+    r, _ = _render(H, WORK_SCENES[name](), cap, stats=True)
+    s = r.stats()
+    return {k: s[k] for k in WORK_COUNTERS}
+
+
+@pytest.mark.parametrize("cap", [3, None])
+@pytest.mark.parametrize("name", sorted(WORK_SCENES))
+def test_executed_work_counters_are_pinned(hip, name, cap):
+    """The executed-work counters under bench.py's FLOP model (sphere, node, box and beam tests, of
+    all rays and of reflected rays) equal the values recorded in tests/golden/work_counters.json
+    from the commit named there: where the searches count their work must not move."""
+    golden = json.loads((GOLDEN / "work_counters.json").read_text())
+    want = golden["cases"][f"{name}_B{cap}"]
+    assert work_counters(hip, name, cap) == want
