@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RTX_ABI_VERSION 2 /* 2: rtx_resolve_samples */
+#define RTX_ABI_VERSION 3 /* 2: rtx_resolve_samples; 3: rtx_last_launches, RTX_WS_COUNTER_BYTES */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -217,7 +217,9 @@ enum {
   RTX_WS_DONE = 2,     /* uint32: finished blocks of the general kernel (reset by the last one) */
   RTX_WS_COUNT2 = 3,   /* uint32: reserved, always zero (not written since the forward fold) */
   RTX_WS_COUNT3 = 4,   /* uint32: rays deferred by the continuation pass (caps above RTX_FAST_MAX_BOUNCES or none) */
-  RTX_WS_HDR_BYTES = 256
+  RTX_WS_HDR_BYTES = 256,
+  RTX_WS_COUNTER_BYTES = 4352 /* RTX_WS_HDR_BYTES and the persistent launches' tile-fetch counters behind it: the
+                                 prefix that is zero after every call, except the sticky status word */
 };
 /* RTX_ST_BAD_SCENE: the scene blob's magic or sphere count (RTX_H_NSPH) disagrees with the
  * n_spheres argument; nothing was rendered. RTX_ST_UNRENDERED: a render passed RTX_F_NO_GENERAL
@@ -461,6 +463,21 @@ int rtx_tiles_timing(void* plan, int slot, float* gather_ms, float* assemble_ms)
  * render kernels use the fast paths (correctly rounded sequences without operand scaling where it
  * is the identity); tests require each pair to agree bit for bit. */
 int rtx_selftest_math(const double* a, const double* b, int64_t n, double* out, void* stream);
+
+/* Test hook: the k_render_fast launches of the calling thread's latest render call
+ * (rtx_render_camera*, rtx_render_frames, rtx_trace_rays, rtx_shade_hits, rtx_tiles_submit), in
+ * launch order, RTX_LAUNCH_WORDS ints each: {B, LDS, DEEP, STATS, TP, IMG, NSPH, WAVES, grid_x,
+ * grid_y, grid_z, n_fetch, tile_order != NULL, lds_bytes}: the template arguments of the
+ * instantiation that was launched, as its launch site names them, then the launch's grid, the
+ * tile-fetch counters in use (0: not a persistent launch), whether it carried a dispatch order, and
+ * its dynamic LDS bytes; *general_out (may be NULL) = 1 if k_render_general was launched. Writes at
+ * most max_records records; returns how many launches there were (a render call launches at most
+ * RTX_LAUNCH_MAX), or RTX_E_ARG for a negative max_records or a null records with max_records > 0.
+ * The state is per calling thread and cleared on entry to every render call; 0 launches before
+ * the thread's first one. */
+#define RTX_LAUNCH_WORDS 14
+#define RTX_LAUNCH_MAX 4
+int rtx_last_launches(int* records, int max_records, int* general_out);
 
 /* Live timing of the dominant render kernel (used by bench.py for the roofline): after
  * rtx_profile_enable(k), the next k render launches hand a hipEvent pair to the k_render_fast

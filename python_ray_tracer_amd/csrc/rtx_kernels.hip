@@ -2469,6 +2469,12 @@ __global__ __launch_bounds__(kBlock) void k_assemble_rows(const uint8_t* __restr
 __attribute__((visibility("hidden"))) hipError_t rtx_launch_small(int B, int deep, bool stats, bool img,
                                                                   const void* params, dim3 grid, uint32_t lds,
                                                                   hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+// The launch record behind rtx_last_launches (a test hook): one entry per k_render_fast launch of the
+// calling thread's current render call, written where the launch names its template arguments (here
+// through launch_k; rtx_small.hip's go<> calls this itself), so it tells which build ran.
+__attribute__((visibility("hidden"))) void rtx_note_launch(int B, int lds, int deep, int stats, int tp, int img,
+                                                           int nsph, int waves, dim3 grid, int n_fetch, int ordered,
+                                                           uint32_t lds_bytes);
 namespace {
 
 // ------------------------------------------------------------------------------------------
@@ -2530,6 +2536,16 @@ inline void prof_next() {
   if (g_prof.on) ++g_prof.used;
   g_prof.on = false;
 }
+
+// rtx_last_launches: the calling thread's latest render call (cleared on its entry; a render call
+// launches k_render_fast once, an uncapped one twice with its continuation pass)
+struct LaunchLog {
+  int n = 0;        // k_render_fast launches
+  int general = 0;  // k_render_general was launched
+  int rec[RTX_LAUNCH_MAX][RTX_LAUNCH_WORDS];
+};
+thread_local LaunchLog g_launches;
+inline void launches_clear() { g_launches.n = g_launches.general = 0; }
 
 
 int device_cus() {  // compute units of the current device (cached per device)
@@ -2594,6 +2610,8 @@ WsLayout ws_layout(int64_t n, int max_bounces) {
 }
 
 size_t ws_bytes(int64_t n, int max_bounces) { return ws_layout(n, max_bounces).total; }
+static_assert(RTX_WS_COUNTER_BYTES == RTX_WS_HDR_BYTES + kMaxFetch * kFetchStride * sizeof(uint32_t),
+              "RTX_WS_COUNTER_BYTES: the header and the tile-fetch counters (ws_layout().list1)");
 
 // The block-tile grid of a camera launch that is not persistent: the TREE = false kernels (scenes below
 // kTreeMinSpheres, launch_fast_lds) use wave_w<false>() pixels per wave row.
@@ -2629,6 +2647,15 @@ dim3 persistent_grid(K kernel, size_t lds, Params& p) {
   return dim3((unsigned)blocks);
 }
 
+// One k_render_fast launch of this unit and its launch record: the template arguments (defaults as
+// the kernel's) are named once, so the record tells the instantiation that ran.
+template <int B, bool LDS, int DEEP, bool STATS = false, int TP = 2, bool IMG = false, int NSPH = 0, int WAVES = 0>
+void launch_k(const Params& p, dim3 grid, uint32_t lds, hipStream_t s) {
+  rtx_note_launch(B, LDS, DEEP, STATS, TP, IMG, NSPH, WAVES, grid, p.n_fetch, p.tile_order != nullptr, lds);
+  hipExtLaunchKernelGGL((k_render_fast<B, LDS, DEEP, STATS, TP, IMG, NSPH, WAVES>), grid, dim3(kFastBlock), lds, s,
+                        prof_event(0), prof_event(1), 0u, p);
+}
+
 // STATS: the instantiation with the per-level and executed-work counters (stats buffer given) and
 // the per-unit cost records (tile_cost given; counters only where p.stats is set).
 // Launches that are not persistent run instantiations without the persistent tile loop (TP 1), and
@@ -2647,19 +2674,16 @@ void launch_fast_lds(Params& p, dim3 grid, hipStream_t s) {
     } else {
       if constexpr (!DEEP && !STATS && !IMG) {
         if ((int64_t)p.n * p.n_frames >= kWavesLargeMinPixels) {  // a large launch: more waves (kFwdWavesLarge)
-          hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, STATS, 1, IMG, 0, kFwdWavesLarge>), grid,
-                                dim3(kFastBlock), (uint32_t)lds, s, prof_event(0), prof_event(1), 0u, p);
+          launch_k<B, true, DEEP, STATS, 1, IMG, 0, kFwdWavesLarge>(p, grid, (uint32_t)lds, s);
           return;
         }
       }
-      hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, STATS, 1, IMG>), grid, dim3(kFastBlock), (uint32_t)lds, s,
-                            prof_event(0), prof_event(1), 0u, p);
+      launch_k<B, true, DEEP, STATS, 1, IMG>(p, grid, (uint32_t)lds, s);
     }
     return;
   }
   if (p.n_fetch > 0) grid = persistent_grid(k_render_fast<B, true, DEEP, STATS, 2, IMG>, lds, p);
-  hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, STATS, 2, IMG>), grid, dim3(kFastBlock), (uint32_t)lds, s,
-                        prof_event(0), prof_event(1), 0u, p);
+  launch_k<B, true, DEEP, STATS, 2, IMG>(p, grid, (uint32_t)lds, s);
 }
 
 template <int B, int DEEP = 0>
@@ -2676,12 +2700,10 @@ void launch_fast_b(const Params& p0, dim3 grid, hipStream_t s) {
   } else {
     if (p.stats || p.tile_cost) {
       if (p.n_fetch > 0) grid = persistent_grid(k_render_fast<B, false, DEEP, true>, 0, p);
-      hipExtLaunchKernelGGL((k_render_fast<B, false, DEEP, true>), grid, dim3(kFastBlock), 0u, s,
-                            prof_event(0), prof_event(1), 0u, p);
+      launch_k<B, false, DEEP, true>(p, grid, 0u, s);
     } else {
       if (p.n_fetch > 0) grid = persistent_grid(k_render_fast<B, false, DEEP>, 0, p);
-      hipExtLaunchKernelGGL((k_render_fast<B, false, DEEP>), grid, dim3(kFastBlock), 0u, s, prof_event(0),
-                            prof_event(1), 0u, p);
+      launch_k<B, false, DEEP>(p, grid, 0u, s);
     }
   }
 }
@@ -2794,11 +2816,22 @@ int run_render(Params& p, void* workspace, size_t workspace_bytes, hipStream_t s
   }
   // deferred rays: ties, and chains longer than the fast kernel's levels
   if (no_general) return RTX_OK;  // (an uncapped render: nor the continuation pass)
+  g_launches.general = 1;
   hipLaunchKernelGGL(k_render_general, dim3((unsigned)(p.n_workers / 64)), dim3(64), 0, s, p);
   return check_launch("k_render_general");
 }
 
 }  // namespace
+
+void rtx_note_launch(int B, int lds, int deep, int stats, int tp, int img, int nsph, int waves, dim3 grid, int n_fetch,
+                     int ordered, uint32_t lds_bytes) {
+  if (g_launches.n < RTX_LAUNCH_MAX) {
+    const int v[RTX_LAUNCH_WORDS] = {B, lds, deep, stats, tp, img, nsph, waves, (int)grid.x, (int)grid.y, (int)grid.z,
+                                     n_fetch, ordered, (int)lds_bytes};
+    for (int k = 0; k < RTX_LAUNCH_WORDS; ++k) g_launches.rec[g_launches.n][k] = v[k];
+  }
+  ++g_launches.n;
+}
 
 // ------------------------------------------------------------------------------------------
 // C ABI
@@ -2889,6 +2922,7 @@ int rtx_render_camera_sched(const double* scene, int n_spheres, int width, int h
                             void* workspace,
                             size_t workspace_bytes, uint64_t* stats, void* stream, unsigned flags,
                             uint32_t* deferred_out, const uint32_t* tile_order, uint32_t* tile_cost) {
+  launches_clear();
   if (width <= 0 || height <= 0 || row_block <= 0 || n_parts <= 0 || part < 0 || part_run < 1 ||
       part_run > n_parts - part || n_local_rows < 0 ||
       n_local_rows > tile_local_rows(height, row_block, n_parts, part, part_run))
@@ -2933,6 +2967,7 @@ int rtx_render_camera(const double* scene, int n_spheres, int width, int height,
 int rtx_render_frames(const double* scenes, int64_t scene_stride, int n_frames, int n_spheres, int width, int height,
                       int max_bounces, void* out, int out_kind, void* workspace, size_t workspace_bytes,
                       uint64_t* stats, void* stream) {
+  launches_clear();
   if (width <= 0 || height <= 0) return fail(RTX_E_ARG, "bad frame geometry%s", "");
   if (n_frames < 0) return fail(RTX_E_ARG, "bad n_frames%s (%lld)", "", n_frames);
   if (n_frames > 1 && scene_stride < RTX_HDR_WORDS) return fail(RTX_E_ARG, "bad scene_stride%s (%lld)", "", scene_stride);
@@ -2960,6 +2995,7 @@ int rtx_render_frames(const double* scenes, int64_t scene_stride, int n_frames, 
 int rtx_trace_rays(const double* scene, int n_spheres, const double* origins, int64_t origin_stride,
                    const double* dirs, int64_t n, int max_bounces, void* out, int out_kind, void* workspace,
                    size_t workspace_bytes, uint64_t* stats, void* stream) {
+  launches_clear();
   if (!origins || !dirs) return fail(RTX_E_ARG, "null ray pointer%s", "");
   if (origin_stride != 0 && origin_stride != n) return fail(RTX_E_ARG, "origin_stride must be 0 or n%s", "");
   Params p{};
@@ -2980,6 +3016,7 @@ int rtx_trace_rays(const double* scene, int n_spheres, const double* origins, in
 int rtx_shade_hits(const double* scene, int n_spheres, int shape, const double* origins, int64_t origin_stride,
                    const double* dirs, const double* t, int64_t n, int max_bounces, void* out, int out_kind,
                    void* workspace, size_t workspace_bytes, uint64_t* stats, void* stream) {
+  launches_clear();
   if (!origins || !dirs || !t) return fail(RTX_E_ARG, "null ray pointer%s", "");
   if (origin_stride != 0 && origin_stride != n) return fail(RTX_E_ARG, "origin_stride must be 0 or n%s", "");
   if (shape < 0 || shape >= n_spheres) return fail(RTX_E_ARG, "shape index out of range%s (%lld)", "", shape);
@@ -3029,6 +3066,16 @@ int rtx_sphere_intersect(const double* sphere, const double* origins, int64_t or
   hipLaunchKernelGGL(k_intersect, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
                      sphere, origins, origin_stride, dirs, n, t_out);
   return check_launch("k_intersect");
+}
+
+int rtx_last_launches(int* records, int max_records, int* general_out) {
+  if (max_records < 0 || (max_records > 0 && !records))
+    return fail(RTX_E_ARG, "rtx_last_launches: null records%s or a negative count (%lld)", "", max_records);
+  const int have = g_launches.n < RTX_LAUNCH_MAX ? g_launches.n : RTX_LAUNCH_MAX;
+  for (int i = 0; i < have && i < max_records; ++i)
+    for (int k = 0; k < RTX_LAUNCH_WORDS; ++k) records[i * RTX_LAUNCH_WORDS + k] = g_launches.rec[i][k];
+  if (general_out) *general_out = g_launches.general;
+  return g_launches.n;
 }
 
 int rtx_selftest_math(const double* a, const double* b, int64_t n, double* out, void* stream) {

@@ -6,11 +6,17 @@
 #define RTX_DEVICE_CODE_ONLY
 #include "rtx_kernels.hip"
 
+// rtx_kernels.hip's launch record (rtx_last_launches)
+__attribute__((visibility("hidden"))) void rtx_note_launch(int B, int lds, int deep, int stats, int tp, int img,
+                                                           int nsph, int waves, dim3 grid, int n_fetch, int ordered,
+                                                           uint32_t lds_bytes);
+
 namespace {
 
 template <int B, int DEEP, bool STATS, bool IMG = false, int NSPH = 0>
 hipError_t go(const void* params, dim3 grid, uint32_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
   const Params& p = *static_cast<const Params*>(params);
+  rtx_note_launch(B, true, DEEP, STATS, 0, IMG, NSPH, 0, grid, p.n_fetch, p.tile_order != nullptr, lds);
   hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, STATS, 0, IMG, NSPH>), grid, dim3(fast_block<false>()), lds, s,
                         e0, e1, 0u, p);
   return hipSuccess;  // launch errors reach the caller's check_launch through hipGetLastError

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 from pathlib import Path
+from typing import NamedTuple
 
 import torch  # noqa: F401  (loads the HIP runtime the library links against)
 
@@ -17,13 +18,16 @@ PKG_DIR = Path(__file__).resolve().parent.parent.parent
 LIB_PATH = Path(os.environ.get("RTX_HIP_LIB", PKG_DIR / "librtx_hip.so"))
 
 # mirrors of include/rtx_hip.h (checked against the library at load time)
-ABI_VERSION = 2
+ABI_VERSION = 3
 HDR_WORDS = 64
 GEOM_WORDS = 8
 MAT_WORDS = 24
 MAX_DOMES = 8
 S_WORDS = 266
 WS_HDR_BYTES = 256
+WS_COUNTER_BYTES = 4352  # the workspace prefix that is zero after every call, except the sticky status word
+LAUNCH_WORDS = 14  # ints per rtx_last_launches record
+LAUNCH_MAX = 4  # k_render_fast launches a render call can make
 FAST_MAX_BOUNCES = 6
 UNBOUNDED_LEVELS = 333
 MAX_SPHERES = 1024
@@ -99,6 +103,7 @@ EXPORTS = (
     "rtx_tiles_destroy",
     "rtx_tiles_timing",
     "rtx_resolve_samples",
+    "rtx_last_launches",
 )
 
 TILES_MAX_SLOTS = 4
@@ -151,6 +156,7 @@ _SIGS = {
     "rtx_tiles_destroy": (_i32, [_c_void_p]),
     "rtx_tiles_timing": (_i32, [_c_void_p, _i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "rtx_resolve_samples": (_i32, [_c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p]),
+    "rtx_last_launches": (_i32, [ctypes.POINTER(_i32), _i32, ctypes.POINTER(_i32)]),
 }
 
 _lib = None
@@ -204,6 +210,38 @@ def profile_collect() -> tuple[float, int]:
     n = _i32()
     check(load().rtx_profile_collect(ctypes.byref(ms), ctypes.byref(n)), "rtx_profile_collect")
     return ms.value, n.value
+
+
+class Launch(NamedTuple):
+    """One rtx_last_launches record: the k_render_fast instantiation a launch site named (B .. WAVES),
+    its grid, the tile-fetch counters in use, whether it carried a dispatch order, its LDS bytes."""
+
+    B: int
+    LDS: int
+    DEEP: int
+    STATS: int
+    TP: int
+    IMG: int
+    NSPH: int
+    WAVES: int
+    grid_x: int
+    grid_y: int
+    grid_z: int
+    n_fetch: int
+    tile_order: int
+    lds_bytes: int
+
+
+def last_launches() -> tuple[list, int]:
+    """(the k_render_fast launches of this thread's latest render call, whether k_render_general was
+    launched): rtx_last_launches, a test hook."""
+    rec = (_i32 * (LAUNCH_WORDS * LAUNCH_MAX))()
+    general = _i32(-1)
+    n = load().rtx_last_launches(rec, LAUNCH_MAX, ctypes.byref(general))
+    check(min(n, 0), "rtx_last_launches")
+    if n > LAUNCH_MAX:
+        raise RtxError(f"rtx_last_launches: {n} launches, more than RTX_LAUNCH_MAX")
+    return [Launch(*rec[i * LAUNCH_WORDS:(i + 1) * LAUNCH_WORDS]) for i in range(n)], general.value
 
 
 def stream_handle(stream=None) -> int:

@@ -366,6 +366,9 @@ class HipRenderer(Renderer):
                 ws[4:8].zero_()  # sticky flags: clear for the next call
             if status & L.ST_BAD_SCENE:
                 raise ValueError("the scene blob's header disagrees with n_spheres: nothing was rendered")
+            if status & L.ST_UNRENDERED:
+                raise RuntimeError("RTX_ST_UNRENDERED: the render passed RTX_F_NO_GENERAL but deferred rays; those "
+                                   "pixels were left unwritten")
             if status & L.ST_STACK_OVERFLOW:
                 raise RecursionError(f"maximum recursion depth exceeded (reflection chain > {L.UNBOUNDED_LEVELS} levels)")
 

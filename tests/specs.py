@@ -1,6 +1,72 @@
 """Scene specs shared by the CPU packer tests and the GPU parity tests."""
 
+import numpy as np
+
 from python_ray_tracer_amd import scenes
+
+
+def fuzz_spec(seed):
+    """A harsher random scene than the bench generator: floating and overlapping spheres of mixed
+    sizes (some huge: always tested by the culling tree), a random light position, 0-2 domes, a
+    random camera (sometimes inside a sphere) and frame size."""
+    rng = np.random.default_rng(1000 + seed)
+    n = int(rng.choice([2, 5, 7, 8, 13, 24, 40]))
+    spec = scenes.random_spec(n, seed, int(rng.integers(9, 57)), int(rng.integers(7, 41)))
+    for sp in spec["spheres"][:-1]:
+        r = float(rng.choice([rng.uniform(0.02, 0.2), rng.uniform(0.2, 1.5), 150.0], p=[0.3, 0.65, 0.05]))
+        sp["radius"] = r
+        sp["center"] = [float(rng.uniform(-4, 4)), float(rng.uniform(-0.5, 3)), float(rng.uniform(0.5, 14))]
+        if r == 150.0:
+            sp["center"][2] += 200.0
+    spec["lights"][0]["position"] = [float(v) for v in rng.uniform([-6, 0.5, -6], [6, 8, 6])]
+    domes = int(rng.integers(0, 3))
+    spec["lights"] = spec["lights"][:1] + [{"kind": "dome", "intensity": float(rng.uniform(0, 0.3)),
+                                            "color": [float(v) for v in rng.uniform(0, 1, 3)]} for _ in range(domes)]
+    cam = [float(rng.uniform(-1.5, 1.5)), float(rng.uniform(-0.3, 1.5)), float(rng.uniform(-4, -0.5))]
+    if seed % 7 == 3:  # camera inside the first sphere
+        spec["spheres"][0]["center"] = [cam[0], cam[1], cam[2] + 0.1]
+        spec["spheres"][0]["radius"] = 0.8
+    spec["camera"]["position"] = cam
+    return spec
+
+
+# the bounce cap each fuzz seed is rendered with (test_fuzz_scenes_against_oracle: seeds 0..13,
+# test_fuzz_scenes_deep_caps: seeds 14..21)
+def fuzz_cap(seed):
+    return [0, 1, 2, 3, 5, 8, 9][seed % 7] if seed < 14 else [None, 12, 20, None][seed % 4]
+
+
+def textured_spec(W, H):
+    """The README scene plus two image-textured spheres (a mirror-ish one and a diffuse one)."""
+    rng = np.random.default_rng(3)
+    img = rng.integers(0, 256, size=(40, 64, 3)).astype(np.float64) / 255.0
+    spec = scenes.readme_spec(W, H)
+    spec["spheres"].insert(0, {"center": [-0.9, 0.2, 2.0], "radius": 0.6,
+                               "shader": {"reflection_gain": 0.0, "specular_gain": 0.0, "specular_roughness": 0.5,
+                                          "iridescence_gain": 0.0, "diffuse_gain": 1.0,
+                                          "texture": {"kind": "image", "texels": img}}})
+    spec["spheres"].insert(1, {"center": [1.2, 0.0, 1.5], "radius": 0.5,
+                               "shader": {"reflection_gain": 0.5, "specular_gain": 0.7, "specular_roughness": 0.2,
+                                          "iridescence_gain": 0.05, "diffuse_gain": 0.8,
+                                          "texture": {"kind": "image", "texels": img[::-1].copy()}}})
+    return spec
+
+
+def trapped_spec(W, H, n_outside=0):
+    """Rays trapped in a radius -5 mirror sphere around the camera, the light at its centre: every
+    chain runs to the bounce cap (test_deep_chains_resume_past_levels_30_and_60). n_outside > 0: as
+    many random_spec spheres moved 20 units further away, outside the trap and never hit (they give the
+    scene its culling tree and, beyond 128 spheres, take the table out of LDS); no ground."""
+    spec = scenes.readme_spec(W, H)
+    spec["spheres"] = [{"center": [0, 0.2, -2], "radius": -5.0,
+                        "shader": {"reflection_gain": 1, "specular_gain": 1.0, "specular_roughness": 0.5,
+                                   "iridescence_gain": 0.05, "diffuse_gain": 0.5,
+                                   "texture": {"kind": "const", "color": [0.9, 0.7, 0.4]}}}]
+    spec["lights"][0]["position"] = [0, 0.2, -2]
+    for sp in scenes.random_spec(n_outside, 3, W, H)["spheres"][:n_outside]:
+        sp["center"][2] += 20.0
+        spec["spheres"].append(sp)
+    return spec
 
 # layouts of huge spheres (radius > scene_pack.HUGE_RADIUS) for RTX_H_NBEAM: (small spheres, huge
 # spheres inserted before the ground, index of one more huge sphere among the small ones or None,

@@ -60,10 +60,14 @@ def test_c1_readme_960x540_full_frame(hip):
 
 
 def test_c3_4k_16_spheres_full_frame(hip):
-    """configs[2]: 3840x2160, 16 spheres + ground, B=4, the whole frame against the oracle. The
-    whole frame's launch (8.3 M pixels) runs the one-tile kernel built for 6 waves/SIMD
-    (kFwdWavesLarge, launches of 4 M pixels and more); three interleaved row tiles of 2.8 M pixels
-    each run the 5-wave build, and give the same rows bit for bit."""
+    """configs[2]: 3840x2160, 16 spheres + ground, B=4, the whole frame against the oracle, rendered
+    by the counting (STATS) build, which has no 6-wave variant. The same frame on a stats-free
+    renderer that learns no order (counter-free from its first launch, 8.3 M pixels) runs the
+    one-tile kernel built for 6 waves/SIMD (kFwdWavesLarge, launches of 4 M pixels and more), as the
+    launch record says, and is bit-identical; three interleaved row tiles of 2.8 M pixels each run
+    the 5-wave build, and give the same rows bit for bit."""
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+
     spec, B = scenes.CONFIGS["C3"]()
     r = hip.HipRenderer(max_bounces=B, collect_stats=True)
     scene = scenes.build_scene(spec)
@@ -74,6 +78,11 @@ def test_c3_4k_16_spheres_full_frame(hip):
     _check(got, want, 3840, 2160, "C3")
     s = r.stats()
     assert s["rays"] == st.rays and s["hits"] == st.hits
+    r6 = hip.HipRenderer(max_bounces=B, learn_tile_order=False)
+    plain = r6.render_tile(scene)
+    (rec,), _ = L.last_launches()
+    assert (rec.WAVES, rec.TP, rec.STATS, rec.B) == (6, 1, 0, B), rec
+    assert torch.equal(plain, frame)
     r5 = hip.HipRenderer(max_bounces=B)
     for part in range(3):
         rows = tiling.tile_rows(2160, 8, 3, part)

@@ -18,6 +18,8 @@ from oracle import numpy_oracle as O
 from python_ray_tracer_amd import scenes
 from tests.conftest import GOLDEN, golden_png
 from tests.specs import HUGE_LAYOUTS, huge_tail_spec
+from tests.specs import fuzz_spec as _fuzz_spec
+from tests.specs import textured_spec as _textured_spec
 
 pytestmark = pytest.mark.gpu
 
@@ -165,17 +167,19 @@ def test_uncapped_skips_continuation_and_general_only_when_nothing_is_deferred(h
 def test_scene_above_the_lds_table(hip, cap):
     """Scenes of more spheres than the LDS table holds (kLdsMaxSpheres = 128) run the builds that read
     the sphere table from global memory. test_large_scene_without_lds_table renders through the
-    counting (STATS) builds; this one through the counter-free builds a plain render runs: the
-    persistent launch (camera frame) and, uncapped, its first pass, continuation pass and general
-    kernel, then the explicit-ray mode (HipCameraRays materialised). 150 spheres against the oracle;
-    the counters of a counting render too."""
+    counting (STATS) builds. Here the renderer's first render is a recording launch (it learns the
+    dispatch order), so it runs the counting build too; the second, with the deferral probe landed
+    and the order learnt, is the counter-free one a plain render runs: the persistent launch (camera
+    frame) and, uncapped, its first pass, continuation pass and general kernel. Then the explicit-ray
+    mode (HipCameraRays materialised), counter-free from its first launch. 150 spheres against the
+    oracle; the counters of a counting render too."""
     spec = scenes.random_spec(150, 7, 56, 32)
     osc = O.scene_from_spec(spec)
     st = O.TraceStats()
     want = O.render(osc, cap, stats=st)
     r = hip.HipRenderer(max_bounces=cap, color_dtype=torch.float64)
     scene = scenes.build_scene(spec)
-    for _ in range(2):  # (the second render with the deferral probe landed)
+    for _ in range(2):  # (the first a recording launch; the second counter-free, the deferral probe landed)
         got = r.render_tile(scene).cpu().numpy()
         assert np.abs(got - want).max() <= ATOL, (cap, np.abs(got - want).max())
     dirs = r.get_ray_directions(scene.camera)
@@ -512,31 +516,6 @@ def test_deep_chains_resume_past_levels_30_and_60(hip, cap):
     assert s["rays"][:n] == st.rays[:n] and s["hits"][:n] == st.hits[:n]
 
 
-def _fuzz_spec(seed):
-    """A harsher random scene than the bench generator: floating and overlapping spheres of mixed
-    sizes (some huge: always tested by the culling tree), a random light position, 0-2 domes, a
-    random camera (sometimes inside a sphere) and frame size."""
-    rng = np.random.default_rng(1000 + seed)
-    n = int(rng.choice([2, 5, 7, 8, 13, 24, 40]))
-    spec = scenes.random_spec(n, seed, int(rng.integers(9, 57)), int(rng.integers(7, 41)))
-    for sp in spec["spheres"][:-1]:
-        r = float(rng.choice([rng.uniform(0.02, 0.2), rng.uniform(0.2, 1.5), 150.0], p=[0.3, 0.65, 0.05]))
-        sp["radius"] = r
-        sp["center"] = [float(rng.uniform(-4, 4)), float(rng.uniform(-0.5, 3)), float(rng.uniform(0.5, 14))]
-        if r == 150.0:
-            sp["center"][2] += 200.0
-    spec["lights"][0]["position"] = [float(v) for v in rng.uniform([-6, 0.5, -6], [6, 8, 6])]
-    domes = int(rng.integers(0, 3))
-    spec["lights"] = spec["lights"][:1] + [{"kind": "dome", "intensity": float(rng.uniform(0, 0.3)),
-                                            "color": [float(v) for v in rng.uniform(0, 1, 3)]} for _ in range(domes)]
-    cam = [float(rng.uniform(-1.5, 1.5)), float(rng.uniform(-0.3, 1.5)), float(rng.uniform(-4, -0.5))]
-    if seed % 7 == 3:  # camera inside the first sphere
-        spec["spheres"][0]["center"] = [cam[0], cam[1], cam[2] + 0.1]
-        spec["spheres"][0]["radius"] = 0.8
-    spec["camera"]["position"] = cam
-    return spec
-
-
 @pytest.mark.parametrize("seed", range(14))
 def test_fuzz_scenes_against_oracle(hip, seed):
     """Random scenes, cameras, sizes and bounce caps (both kernels; culled and linear sphere
@@ -699,22 +678,6 @@ def test_shader_create_matches_reference(hip):
     with pytest.raises(ValueError):
         scene.shapes[0].shader.create(hip.HipSphere(hip.HipVector3D(0, 0, 0), 1.0, None), scene,
                                       hip.HipVector3D(*sc.cam), hip.HipVector3D(*dd), t[hit], r)
-
-
-def _textured_spec(W, H):
-    """The README scene plus two image-textured spheres (a mirror-ish one and a diffuse one)."""
-    rng = np.random.default_rng(3)
-    img = rng.integers(0, 256, size=(40, 64, 3)).astype(np.float64) / 255.0
-    spec = scenes.readme_spec(W, H)
-    spec["spheres"].insert(0, {"center": [-0.9, 0.2, 2.0], "radius": 0.6,
-                               "shader": {"reflection_gain": 0.0, "specular_gain": 0.0, "specular_roughness": 0.5,
-                                          "iridescence_gain": 0.0, "diffuse_gain": 1.0,
-                                          "texture": {"kind": "image", "texels": img}}})
-    spec["spheres"].insert(1, {"center": [1.2, 0.0, 1.5], "radius": 0.5,
-                               "shader": {"reflection_gain": 0.5, "specular_gain": 0.7, "specular_roughness": 0.2,
-                                          "iridescence_gain": 0.05, "diffuse_gain": 0.8,
-                                          "texture": {"kind": "image", "texels": img[::-1].copy()}}})
-    return spec
 
 
 @pytest.mark.parametrize("B", [3, None])

@@ -75,8 +75,48 @@ def test_abi_layout_matches_header():
     assert const("RTX_H_SBOX") == L.H_SBOX
     assert const("RTX_MAGIC") == L.MAGIC
     assert const("RTX_UNBOUNDED_LEVELS") == L.UNBOUNDED_LEVELS
+    assert const("RTX_WS_HDR_BYTES") == L.WS_HDR_BYTES
+    assert const("RTX_WS_COUNTER_BYTES") == L.WS_COUNTER_BYTES == L.WS_HDR_BYTES + 32 * 32 * 4
+    assert const("RTX_LAUNCH_WORDS") == L.LAUNCH_WORDS == len(L.Launch._fields)
+    assert const("RTX_LAUNCH_MAX") == L.LAUNCH_MAX
+    assert const("RTX_ABI_VERSION") == L.ABI_VERSION == 3
+    # the record's fields in the header's order
+    doc = re.search(r"RTX_LAUNCH_WORDS ints each: \{([^}]*)\}", text).group(1)
+    names = [re.sub(r"\W+", " ", w).split()[0] for w in doc.replace("*", "").split(",")]
+    assert names == list(L.Launch._fields), names
     lay = (ctypes.c_int * 8)()
     assert L.load().rtx_abi_version(lay, 8) == L.ABI_VERSION
+
+
+def test_last_launches_before_any_render_and_argument_checks():
+    """rtx_last_launches (the launch record, a test hook): no launch before a thread's first render
+    call, a null record buffer is refused unless nothing is asked for, and a render call that fails
+    its argument checks leaves an empty record."""
+    import threading
+
+    lib = L.load()
+    got = {}
+
+    def fresh_thread():  # thread-local state: a new thread has never rendered
+        gen = ctypes.c_int(7)
+        rec = (ctypes.c_int * (L.LAUNCH_WORDS * L.LAUNCH_MAX))()
+        got["n"] = lib.rtx_last_launches(rec, L.LAUNCH_MAX, ctypes.byref(gen))
+        got["general"] = gen.value
+        got["helper"] = L.last_launches()
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert got == {"n": 0, "general": 0, "helper": ([], 0)}
+    assert L.last_launches() == ([], 0)  # this thread: no CPU test launches anything
+    gen = ctypes.c_int(7)
+    assert lib.rtx_last_launches(None, 1, ctypes.byref(gen)) == -1 and b"rtx_last_launches" in lib.rtx_last_error()
+    assert gen.value == 7
+    assert lib.rtx_last_launches(None, 0, None) == 0  # only the count
+    rec = (ctypes.c_int * L.LAUNCH_WORDS)()
+    assert lib.rtx_last_launches(rec, -1, None) == -1
+    assert lib.rtx_render_camera(None, 3, 16, 16, 1, 1, 0, 16, 3, None, 0, None, 0, None, None) == -1
+    assert L.last_launches() == ([], 0)
 
 
 def test_workspace_bytes_and_error_paths():
