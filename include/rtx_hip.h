@@ -20,6 +20,11 @@
  *                                                             (base.py:143-151)
  *   rtx_resolve_samples <- no counterpart: the box filter of supersampled anti-aliasing
  *                          (HipRenderer(samples=k)); each sample clipped as save_image clips a pixel
+ *   rtx_primary_aovs, rtx_primary_aovs_rays
+ *                       <- no counterpart: the primary hit's intermediates as render passes — the
+ *                          nearest distance and hit shape of raytrace_scene (base.py:97-103), P, the
+ *                          normal and is_in_light of NumpyShader.create (shader.py:73-84) and
+ *                          Texture.get_color — which the reference computes and discards
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -370,6 +375,54 @@ int rtx_quantize_u8(const void* color, int color_kind, int64_t n, uint8_t* out, 
  * size, an unknown out_kind, or k*k*width*n_rows*n_frames >= 2^31. */
 int rtx_resolve_samples(const double* samples, int k, int width, int n_rows, int n_frames,
                         void* out, int out_kind, void* stream);
+
+/* Primary-hit render passes (HipRenderer.render_aovs / trace_aovs; the reference returns the
+ * finished colour only): the intermediates of the level-0 ray of every pixel, each defined by the
+ * reference's own expression and computed in float64 in its operation order, without contraction.
+ * With distances[s] = shapes[s].intersect(O, D) (shape.py:28-51) over the S shapes in scene order:
+ *   depth    double [n]     nearest = reduce(np.minimum, distances) (base.py:98); a miss is exactly
+ *                           1e39 (FARAWAY)
+ *   id       int32  [n]     the smallest s with distances[s] == nearest where nearest != FARAWAY
+ *                           (base.py:102-103); a miss is -1
+ *   hits     int32  [n]     how many shapes have distances[s] == nearest: 0 on a miss, more than 1 on
+ *                           a tie (the reference shades and sums every one of them, base.py:119)
+ *   position double [3][n]  P = O + D * nearest (shader.py:73)
+ *   normal   double [3][n]  N = (P - C) * (1.0 / radius) of shape id (shader.py:74; not renormalised,
+ *                           and pointing inwards for a negative radius)
+ *   albedo   double [3][n]  shapes[id].shader.diffuse_color.get_color(P): the constant colour
+ *                           (shader.py:17-19), the checker cell as 1.0 / 0.0 in all three channels
+ *                           (shader.py:30-32), or the image texel of NumpyTexturedSphere's mapping
+ *                           (shape.py:66-79; atan2 / asin are not correctly rounded on either side, so
+ *                           a point within an ulp of a texel edge may take the neighbour texel)
+ *   lit      uint8  [n]     is_in_light (shader.py:75-84, 126-128): with L = norm(lights[0] - P) and
+ *                           the nudged origin P + N * 0.0001, light_distances[id] ==
+ *                           min(light_distances) over all S shapes; 1 or 0
+ * On a miss position, normal and albedo are 0.0 and lit is 0. On a tie the per-hit passes (position,
+ * normal, albedo, lit) are those of shape id, the first of the tied shapes in scene order. The passes
+ * stop at level 0: no reflected ray is traced.
+ * Every output pointer may be NULL: that pass is not requested, costs no store, and a call without
+ * lit traces no shadow ray, one without albedo looks up no texel. The RTX_AOV_* bits name the passes
+ * for the layers above (rt::primary_aovs's `passes` mask; results in bit order).
+ * rtx_primary_aovs: the camera rays of one row tile, the tile geometry and local row order of
+ * rtx_render_camera_sched (n = width * n_local_rows). rtx_primary_aovs_rays: n explicit rays in the
+ * layout of rtx_trace_rays (origin_stride 0 or n).
+ * A blob whose magic or sphere count disagrees with n_spheres is traced as an empty scene (every ray
+ * a miss). Needs no workspace; asynchronous on `stream`, never allocates, never synchronises.
+ * RTX_E_ARG (before any HIP call) for a null scene or null rays, all seven output pointers null,
+ * n_spheres outside 1..RTX_MAX_SPHERES, bad tile geometry, an origin_stride other than 0 or n, or a
+ * negative n; zero rays return RTX_OK without a launch. */
+enum {
+  RTX_AOV_DEPTH = 1, RTX_AOV_ID = 2, RTX_AOV_HITS = 4, RTX_AOV_POSITION = 8, RTX_AOV_NORMAL = 16,
+  RTX_AOV_ALBEDO = 32, RTX_AOV_LIT = 64, RTX_AOV_ALL = 127
+};
+int rtx_primary_aovs(const double* scene, int n_spheres, int width, int height,
+                     int row_block, int n_parts, int part, int part_run, int n_local_rows,
+                     double* depth, int32_t* id, int32_t* hits, double* position, double* normal,
+                     double* albedo, uint8_t* lit, void* stream);
+int rtx_primary_aovs_rays(const double* scene, int n_spheres, const double* origins, int64_t origin_stride,
+                          const double* dirs, int64_t n,
+                          double* depth, int32_t* id, int32_t* hits, double* position, double* normal,
+                          double* albedo, uint8_t* lit, void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

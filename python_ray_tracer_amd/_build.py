@@ -13,6 +13,7 @@ REPO = PKG.parent
 SRC = PKG / "csrc" / "rtx_kernels.hip"
 SMALL_SRC = PKG / "csrc" / "rtx_small.hip"  # includes SRC's device code
 TILES_SRC = PKG / "csrc" / "rtx_tiles.hip"  # host code: the row-tiled multi-GPU frame (RCCL at run time)
+AOV_SRC = PKG / "csrc" / "rtx_aov.hip"  # includes SRC's device code: k_primary_aovs and its entry points
 HDR = REPO / "include" / "rtx_hip.h"
 LIB = PKG / "librtx_hip.so"
 OPS_SRC = PKG / "csrc" / "rt_ops.cpp"
@@ -43,7 +44,7 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    return any(p.stat().st_mtime > t for p in (SRC, SMALL_SRC, TILES_SRC, HDR, Path(__file__)))
+    return any(p.stat().st_mtime > t for p in (SRC, SMALL_SRC, TILES_SRC, AOV_SRC, HDR, Path(__file__)))
 
 
 OBJ_CACHE = PKG / ".objcache"  # compiled units by content hash (a one-unit change rebuilds one unit)
@@ -70,15 +71,19 @@ def _unit_key(src: Path, flags) -> str:
 
 
 def compile_units(out: Path, main_src: Path, small_src: Path | None, extra_flags=(), verbose: bool = False,
-                  small_flags=None) -> None:
+                  small_flags=None, aov_src: Path | None = None) -> None:
     """Compile the library's translation units to objects (in parallel) and link ``out``: main_src
-    with HIPCC_FLAGS, small_src (None: a single-unit source) with SMALL_FLAGS (or small_flags) added."""
+    with HIPCC_FLAGS, small_src (None: a single-unit source) with SMALL_FLAGS (or small_flags) added,
+    aov_src (the render-pass unit, which includes main_src's device code like small_src; None: a
+    revision without it) with HIPCC_FLAGS."""
     import tempfile
 
     sf = list(SMALL_FLAGS if small_flags is None else small_flags)
     units = [(main_src, [])] + ([(small_src, sf)] if small_src is not None else [])
     if small_src is not None and TILES_SRC.exists():  # (single-unit revisions of the A/B tool build alone)
         units.append((TILES_SRC, []))
+    if aov_src is not None:
+        units.append((aov_src, []))
     objs, procs = [], []
     # objects in a directory of this call's own: concurrent builds (several ranks importing on a
     # fresh checkout) cannot overwrite or delete each other's objects before the link
@@ -122,7 +127,7 @@ def build_library(force: bool = False, extra_flags=(), out: Path | None = None, 
         return out
     tmp = out.with_suffix(f".so.tmp{os.getpid()}")  # per process: concurrent builds each rename a whole file
     try:
-        compile_units(tmp, SRC, SMALL_SRC, extra_flags, verbose)
+        compile_units(tmp, SRC, SMALL_SRC, extra_flags, verbose, aov_src=AOV_SRC)
         os.replace(tmp, out)
     finally:
         tmp.unlink(missing_ok=True)

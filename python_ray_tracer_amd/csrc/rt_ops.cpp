@@ -13,6 +13,10 @@
 //                        equal shares or weighted ones (root_run / run: rtx_assemble_runs)
 //   rt::resolve_samples <- no counterpart: the box filter of a k x k supersampled frame
 //                        (HipRenderer(samples=k), rtx_resolve_samples)
+//   rt::primary_aovs, rt::primary_aovs_rays
+//                     <- no counterpart: the primary hit's intermediates as render passes (depth, id,
+//                        hits, position, normal, albedo, lit; rtx_primary_aovs), for a row tile of the
+//                        camera's frame or for explicit rays
 //   rt::status        <- reads and clears the workspace's sticky RTX_ST_* flags
 //   rt::comm_unique_id, rt::comm_init, rt::comm_destroy, rt::tiles_create, rt::tiles_submit,
 //   rt::tiles_finish, rt::tiles_destroy
@@ -405,6 +409,72 @@ at::Tensor resolve_samples(const at::Tensor& samples, int64_t k, int64_t width, 
   return out;
 }
 
+// ---- primary-hit render passes (rtx_primary_aovs) ----------------------------------------------
+// `passes`: a mask of RTX_AOV_* bits; the result holds one tensor per set bit, in bit order: depth
+// float64 [n], id int32 [n], hits int32 [n], position / normal / albedo float64 [3, n], lit uint8 [n].
+// Shared by the kernels and their Meta forms.
+std::vector<at::Tensor> new_aovs(const at::Tensor& like, int64_t n, int64_t passes) {
+  TORCH_CHECK(passes > 0 && (passes & ~(int64_t)RTX_AOV_ALL) == 0, "passes must be a non-empty mask of RTX_AOV_* bits (1..",
+              (int)RTX_AOV_ALL, "), got ", passes);
+  const auto o = like.options();
+  std::vector<at::Tensor> out;
+  if (passes & RTX_AOV_DEPTH) out.push_back(at::empty({n}, o.dtype(at::kDouble)));
+  if (passes & RTX_AOV_ID) out.push_back(at::empty({n}, o.dtype(at::kInt)));
+  if (passes & RTX_AOV_HITS) out.push_back(at::empty({n}, o.dtype(at::kInt)));
+  if (passes & RTX_AOV_POSITION) out.push_back(at::empty({3, n}, o.dtype(at::kDouble)));
+  if (passes & RTX_AOV_NORMAL) out.push_back(at::empty({3, n}, o.dtype(at::kDouble)));
+  if (passes & RTX_AOV_ALBEDO) out.push_back(at::empty({3, n}, o.dtype(at::kDouble)));
+  if (passes & RTX_AOV_LIT) out.push_back(at::empty({n}, o.dtype(at::kByte)));
+  return out;
+}
+
+// the seven output pointers of `out` (new_aovs(passes)), null where a pass is not requested
+struct AovPtrs {
+  void* p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  AovPtrs(const std::vector<at::Tensor>& out, int64_t passes) {
+    size_t k = 0;
+    for (int b = 0; b < 7; ++b)
+      if (passes & (int64_t(1) << b)) p[b] = out[k++].data_ptr();
+  }
+};
+
+std::vector<at::Tensor> primary_aovs(const at::Tensor& scene, int64_t n_spheres, int64_t width, int64_t height,
+                                     int64_t row_block, int64_t n_parts, int64_t part, int64_t part_run,
+                                     int64_t passes, bool check) {
+  check_scene(scene, n_spheres);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  check_tile(width, height, row_block, n_parts, part, part_run);
+  const int64_t rows = tile_rows(height, row_block, n_parts, part, part_run);
+  std::vector<at::Tensor> out = new_aovs(scene, width * rows, passes);
+  if (check) check_headers(scene, n_spheres);
+  if (rows == 0) return out;  // an empty tile: nothing to launch (an empty tensor's pointer may be null)
+  const AovPtrs a(out, passes);
+  check_rc(rtx_primary_aovs(scene.data_ptr<double>(), (int)n_spheres, (int)width, (int)height, (int)row_block,
+                            (int)n_parts, (int)part, (int)part_run, (int)rows, (double*)a.p[0], (int32_t*)a.p[1],
+                            (int32_t*)a.p[2], (double*)a.p[3], (double*)a.p[4], (double*)a.p[5], (uint8_t*)a.p[6],
+                            stream_of(scene)),
+           "rtx_primary_aovs");
+  return out;
+}
+
+std::vector<at::Tensor> primary_aovs_rays(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& origins,
+                                          const at::Tensor& dirs, int64_t passes, bool check) {
+  check_scene(scene, n_spheres);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  const int64_t stride = check_rays(scene, origins, dirs);
+  const int64_t n = dirs.size(1);
+  std::vector<at::Tensor> out = new_aovs(scene, n, passes);
+  if (check) check_headers(scene, n_spheres);
+  if (n == 0) return out;
+  const AovPtrs a(out, passes);
+  check_rc(rtx_primary_aovs_rays(scene.data_ptr<double>(), (int)n_spheres, origins.data_ptr<double>(), stride,
+                                 dirs.data_ptr<double>(), n, (double*)a.p[0], (int32_t*)a.p[1], (int32_t*)a.p[2],
+                                 (double*)a.p[3], (double*)a.p[4], (double*)a.p[5], (uint8_t*)a.p[6],
+                                 stream_of(scene)),
+           "rtx_primary_aovs_rays");
+  return out;
+}
+
 int64_t status(at::Tensor& workspace) {
   check_gpu(workspace, "workspace", at::kByte);
   TORCH_CHECK(workspace.numel() >= RTX_WS_HDR_BYTES, "workspace shorter than its header");
@@ -564,6 +634,21 @@ at::Tensor resolve_samples_meta(const at::Tensor& samples, int64_t k, int64_t wi
   return new_output(samples, rows * width, rows, width, out_kind, frames);
 }
 
+std::vector<at::Tensor> primary_aovs_meta(const at::Tensor& scene, int64_t n_spheres, int64_t width, int64_t height,
+                                          int64_t row_block, int64_t n_parts, int64_t part, int64_t part_run,
+                                          int64_t passes, bool) {
+  check_scene_shape(scene, n_spheres);
+  check_tile(width, height, row_block, n_parts, part, part_run);
+  return new_aovs(scene, width * tile_rows(height, row_block, n_parts, part, part_run), passes);
+}
+
+std::vector<at::Tensor> primary_aovs_rays_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor&,
+                                               const at::Tensor& dirs, int64_t passes, bool) {
+  check_scene_shape(scene, n_spheres);
+  TORCH_CHECK(dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be [3, n]");
+  return new_aovs(scene, dirs.size(1), passes);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rt, m) {
@@ -581,6 +666,10 @@ TORCH_LIBRARY(rt, m) {
   m.def("assemble_rows(Tensor tiles, int width, int height, int row_block, int out_kind, int root_run=1, "
         "int run=1) -> Tensor");
   m.def("resolve_samples(Tensor samples, int k, int width, int rows, int out_kind) -> Tensor");
+  m.def("primary_aovs(Tensor scene, int n_spheres, int width, int height, int row_block, int n_parts, int part, "
+        "int part_run, int passes, bool check=True) -> Tensor[]");
+  m.def("primary_aovs_rays(Tensor scene, int n_spheres, Tensor origins, Tensor dirs, int passes, "
+        "bool check=True) -> Tensor[]");
   m.def("status(Tensor(a!) workspace) -> int");
   m.def("workspace_bytes(int n_rays, int max_bounces) -> int", &workspace_bytes);
   // the row-tiled multi-GPU frame (one native call per frame and rank; handles are int64)
@@ -607,6 +696,8 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("quantize_u8", &quantize_u8);
   m.impl("assemble_rows", &assemble_rows);
   m.impl("resolve_samples", &resolve_samples);
+  m.impl("primary_aovs", &primary_aovs);
+  m.impl("primary_aovs_rays", &primary_aovs_rays);
   m.impl("status", &status);
 }
 
@@ -621,6 +712,8 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("quantize_u8", &quantize_u8);
   m.impl("assemble_rows", &assemble_rows);
   m.impl("resolve_samples", &resolve_samples);
+  m.impl("primary_aovs", &primary_aovs);
+  m.impl("primary_aovs_rays", &primary_aovs_rays);
   m.impl("status", &status);
 }
 
@@ -633,4 +726,6 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("quantize_u8", &quantize_u8_meta);
   m.impl("assemble_rows", &assemble_rows_meta);
   m.impl("resolve_samples", &resolve_samples_meta);
+  m.impl("primary_aovs", &primary_aovs_meta);
+  m.impl("primary_aovs_rays", &primary_aovs_rays_meta);
 }

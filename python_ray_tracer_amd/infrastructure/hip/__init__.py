@@ -9,6 +9,7 @@ Reference module -> this module:
 """
 
 from .base import (
+    AOV_NAMES,
     FARAWAY,
     HipCameraRays,
     HipRenderer,
@@ -20,6 +21,7 @@ from .shader import HipShader, ImageTexture, Texture, TextureChecker
 from .shape import HipSphere, HipTexturedSphere
 
 __all__ = [
+    "AOV_NAMES",
     "FARAWAY",
     "HipCameraRays",
     "HipRenderer",

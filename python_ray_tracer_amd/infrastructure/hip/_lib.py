@@ -104,7 +104,15 @@ EXPORTS = (
     "rtx_tiles_timing",
     "rtx_resolve_samples",
     "rtx_last_launches",
+    "rtx_primary_aovs",
+    "rtx_primary_aovs_rays",
 )
+
+# RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
+AOV_DEPTH, AOV_ID, AOV_HITS, AOV_POSITION, AOV_NORMAL, AOV_ALBEDO, AOV_LIT = 1, 2, 4, 8, 16, 32, 64
+AOV_ALL = 127
+AOV_PASSES = {"depth": AOV_DEPTH, "id": AOV_ID, "hits": AOV_HITS, "position": AOV_POSITION,
+              "normal": AOV_NORMAL, "albedo": AOV_ALBEDO, "lit": AOV_LIT}
 
 TILES_MAX_SLOTS = 4
 TILES_LOOPBACK = 1  # rtx_tiles_create flags
@@ -157,6 +165,10 @@ _SIGS = {
     "rtx_tiles_timing": (_i32, [_c_void_p, _i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "rtx_resolve_samples": (_i32, [_c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p]),
     "rtx_last_launches": (_i32, [ctypes.POINTER(_i32), _i32, ctypes.POINTER(_i32)]),
+    "rtx_primary_aovs": (_i32, [_c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p,
+                                _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "rtx_primary_aovs_rays": (_i32, [_c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p,
+                                     _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 _lib = None

@@ -21,6 +21,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
 * ``color_dtype`` float64 (default, the reference dtype) or float32.
 * ``HipRenderer(samples=k)``: supersampled anti-aliasing, k x k samples per pixel, box-filtered
   (the reference traces one ray per pixel).
+* ``HipRenderer.render_aovs`` / ``trace_aovs``: the primary hit's intermediates (depth, id, hits,
+  position, normal, albedo, lit) as render passes; the reference computes and discards them.
 """
 
 from __future__ import annotations
@@ -41,6 +43,7 @@ from . import _lib as L
 from .scene_pack import camera_words, pack_key, scene_key
 
 FARAWAY = 1.0e39  # base.py:12
+AOV_NAMES = tuple(L.AOV_PASSES)  # the primary-hit passes of render_aovs / trace_aovs, in result order
 
 
 def _is_tensor(x) -> bool:
@@ -685,6 +688,68 @@ class HipRenderer(Renderer):
         self._check_status(ws)
         return res
 
+    # ---------------------------------------------------------------- primary-hit render passes
+    def _aov_tensors(self, names, n: int) -> dict:
+        shapes = {"depth": ((n,), torch.float64), "id": ((n,), torch.int32), "hits": ((n,), torch.int32),
+                  "position": ((3, n), torch.float64), "normal": ((3, n), torch.float64),
+                  "albedo": ((3, n), torch.float64), "lit": ((n,), torch.uint8)}
+        return {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in names}
+
+    @_on_device
+    def render_aovs(self, scene, passes=AOV_NAMES, row_block: int = 1, n_parts: int = 1, part: int = 0,
+                    part_run: int = 1) -> dict:
+        """The primary-hit render passes of the scene camera's frame (rtx_primary_aovs), or of the row
+        tile ``part`` .. ``part + part_run - 1`` of ``n_parts`` (rows in local order, as render_tile):
+        a dict of device tensors, one per name in ``passes`` (any of ``AOV_NAMES``, default all), in
+        that fixed order. For the level-0 ray of each pixel, in the reference's float64 expressions:
+
+        * ``depth`` float64 [n]: the nearest distance (base.py:98); exactly FARAWAY on a miss
+        * ``id`` int32 [n]: the first shape in scene order at that distance (base.py:102-103); -1 on a miss
+        * ``hits`` int32 [n]: how many shapes are at that distance (0 on a miss, more than 1 on a tie)
+        * ``position`` / ``normal`` float64 [3, n]: P and (P - C) * (1 / radius) (shader.py:73-74)
+        * ``albedo`` float64 [3, n]: diffuse_color.get_color(P) (constant, checker cell, image texel)
+        * ``lit`` uint8 [n]: is_in_light (shader.py:75-84, 126-128)
+
+        On a miss position, normal and albedo are 0.0 and lit is 0; on a tie the per-hit passes are
+        those of shape ``id``. A pass that is not requested is neither computed nor stored (no shadow
+        ray without ``lit``, no texel lookup without ``albedo``). One launch, no workspace, whatever
+        the bounce cap. Raises ValueError on a ``samples >= 2`` renderer (an average of ids or normals
+        over samples is not defined) and for an unknown pass name."""
+        self._need_camera("render_aovs")
+        names = _aov_names(passes)
+        blob, S = self.scene_blob(scene)
+        W, H = int(scene.camera.width), int(scene.camera.height)
+        rows = n_local_rows(H, row_block, n_parts, part, part_run)
+        out = self._aov_tensors(names, W * rows)
+        if rows:  # (an empty tile launches nothing)
+            L.check(self._lib.rtx_primary_aovs(blob.data_ptr(), S, W, H, row_block, n_parts, part, part_run, rows,
+                                               *(_ptr(out.get(k)) for k in AOV_NAMES), self._stream()),
+                    "rtx_primary_aovs")
+        return out
+
+    @_on_device
+    def trace_aovs(self, ray_origin, dirs, scene, passes=AOV_NAMES) -> dict:
+        """render_aovs for explicit rays (rtx_primary_aovs_rays): the same inputs as raytrace_scene —
+        a shared origin (scalars) or one per ray, and [3, n] directions — and the same dict of passes
+        for the first hit of each ray."""
+        self._need_camera("trace_aovs")
+        names = _aov_names(passes)
+        blob, S = self.scene_blob(scene)
+        D = _as_vector(dirs).to_tensor(self.device)
+        if D.dim() != 2:
+            D = D.reshape(3, 1)
+        n = D.shape[1]
+        O = _as_vector(ray_origin).to_tensor(self.device, n)
+        stride = 0 if O.dim() == 1 else n
+        if stride and O.shape[1] != n:
+            raise ValueError(f"origins ({O.shape[1]}) and directions ({n}) differ in length")
+        out = self._aov_tensors(names, n)
+        if n:
+            L.check(self._lib.rtx_primary_aovs_rays(blob.data_ptr(), S, O.data_ptr(), stride, D.data_ptr(), n,
+                                                    *(_ptr(out.get(k)) for k in AOV_NAMES), self._stream()),
+                    "rtx_primary_aovs_rays")
+        return out
+
     def _override_blob(self, scene, si, shape, shader):
         """The scene blob with a level-0 material record for ``shader`` (scene_pack.pack_override),
         cached by content like scene_blob."""
@@ -781,6 +846,17 @@ class HipRenderer(Renderer):
     def reset_stats(self) -> None:
         if self.stats_buffer is not None:
             self.stats_buffer.zero_()
+
+
+def _aov_names(passes) -> tuple:
+    """The requested passes in the fixed order of AOV_NAMES; ValueError for an unknown or missing name."""
+    if isinstance(passes, str):
+        passes = (passes,)
+    passes = tuple(passes)
+    bad = [p for p in passes if p not in L.AOV_PASSES]
+    if bad or not passes:
+        raise ValueError(f"passes: need one or more of {AOV_NAMES}, got {passes!r}")
+    return tuple(k for k in AOV_NAMES if k in passes)
 
 
 def _sample_scene(scene, k: int) -> Scene3D:

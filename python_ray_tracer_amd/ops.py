@@ -33,6 +33,14 @@ that device's current HIP stream and returns a new tensor):
   every sample clipped to [0, 1], the k*k of a pixel summed row by row and divided once;
   [3, rows*width] / [F, 3, rows*width] colour (out_kind 0, 1) or [rows, width, 3] /
   [F, rows, width, 3] uint8 (out_kind 2). Needs no workspace and raises on a short ``samples``.
+* ``rt::primary_aovs(scene, n_spheres, width, height, row_block, n_parts, part, part_run, passes,
+  check=True)`` and ``rt::primary_aovs_rays(scene, n_spheres, origins, dirs, passes, check=True)`` —
+  the primary hit's intermediates as render passes (rtx_primary_aovs; HipRenderer.render_aovs /
+  trace_aovs), for a row tile of the camera's frame (local row order, as render_tile) or for explicit
+  rays (origins [3] or [3, n]). ``passes`` is a mask of the RTX_AOV_* bits (``_lib.AOV_*``): 1 depth
+  float64 [n], 2 id int32 [n], 4 hits int32 [n], 8 position, 16 normal, 32 albedo float64 [3, n],
+  64 lit uint8 [n]; the result is a list with one tensor per set bit, in bit order. A pass that is
+  not requested is neither computed nor stored. Need no workspace.
 * ``rt::status(workspace)`` — reads and clears the sticky RTX_ST_* flags (1 stack overflow,
   2 deferred-list overflow, 4 bad scene); synchronises.
 * ``rt::workspace_bytes(n_rays, max_bounces)``.
@@ -61,7 +69,7 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "resolve_samples", "status", "workspace_bytes",
+       "resolve_samples", "primary_aovs", "primary_aovs_rays", "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
        "comm_unique_id", "comm_init", "comm_destroy", "tiles_create", "tiles_submit", "tiles_finish",
        "tiles_destroy")

@@ -84,14 +84,25 @@ def main():
                      if a.rev else _build.SMALL_SRC.read_text())
         small = _build.SRC.with_name(f"_ab_{Path(a.out).stem}_small.hip")
         small.write_text(small_src.replace('#include "rtx_kernels.hip"', f'#include "{tmp.name}"'))
+    # ... and the render-pass unit (rtx_aov.hip, which includes the kernel file the same way), when the
+    # revision has one: _lib.load binds its entry points
+    aov = None
+    if small is not None:
+        shown = (subprocess.run(["git", "show", f"{a.rev}:{_build.AOV_SRC.relative_to(REPO)}"], cwd=REPO,
+                                capture_output=True, text=True) if a.rev else None)
+        aov_src = _build.AOV_SRC.read_text() if shown is None else shown.stdout if shown.returncode == 0 else None
+        if aov_src is not None:
+            aov = _build.SRC.with_name(f"_ab_{Path(a.out).stem}_aov.hip")
+            aov.write_text(aov_src.replace('#include "rtx_kernels.hip"', f'#include "{tmp.name}"'))
     try:
         out = Path(a.out).resolve()
         out.parent.mkdir(parents=True, exist_ok=True)
-        _build.compile_units(out, tmp, small, a.flag, small_flags=a.small_flag)
+        _build.compile_units(out, tmp, small, a.flag, small_flags=a.small_flag, aov_src=aov)
     finally:
         tmp.unlink(missing_ok=True)
-        if small is not None:
-            small.unlink(missing_ok=True)
+        for unit in (small, aov):
+            if unit is not None:
+                unit.unlink(missing_ok=True)
     print(out)
 
 
