@@ -25,6 +25,10 @@
  *                          nearest distance and hit shape of raytrace_scene (base.py:97-103), P, the
  *                          normal and is_in_light of NumpyShader.create (shader.py:73-84) and
  *                          Texture.get_color — which the reference computes and discards
+ *   rtx_edge_mask, rtx_sample_dirs, rtx_resolve_scatter
+ *                       <- no counterpart: adaptive anti-aliasing (HipRenderer(samples=k,
+ *                          adaptive=True)): which pixels of a plain frame are edges, the k x k sample
+ *                          rays of those pixels, and their resolve written back over the frame
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -55,6 +59,8 @@ extern "C" {
 #endif
 
 #define RTX_ABI_VERSION 3 /* 2: rtx_resolve_samples; 3: rtx_last_launches, RTX_WS_COUNTER_BYTES */
+/* (rtx_primary_aovs*, rtx_edge_mask, rtx_sample_dirs and rtx_resolve_scatter were added to version 3:
+ * new symbols only, nothing that existed changed) */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -423,6 +429,49 @@ int rtx_primary_aovs_rays(const double* scene, int n_spheres, const double* orig
                           const double* dirs, int64_t n,
                           double* depth, int32_t* id, int32_t* hits, double* position, double* normal,
                           double* albedo, uint8_t* lit, void* stream);
+
+/* Adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True); the reference renders
+ * one sample per pixel): only the edge pixels of a frame get k x k samples. The contract:
+ *  1. Base frame. B is the plain float64 render at width x height (unclipped), cb = clip01(B) with a
+ *     NaN sent to 0 as the resolve sends it; id, hits and lit are rtx_primary_aovs' passes of the
+ *     same frame.
+ *  2. Mask (rtx_edge_mask). Pixel p = (r, c) is flagged if hits[p] > 1, or if some neighbour
+ *     q = (r + dr, c + dc) inside the frame, dr, dc in {-1, 0, 1} and not both 0, has id[q] != id[p],
+ *     or lit[q] != lit[p], or max over the channels of |cb[ch][q] - cb[ch][p]| > contrast. The colour
+ *     comparison is strict and in float64; contrast = +inf turns it off. The criterion is symmetric:
+ *     both sides of an edge are flagged. A 1 x 1 frame flags only a tie.
+ *  3. Samples (rtx_sample_dirs). The flagged pixels are listed in ascending pixel index. Ray
+ *     j*k*k + sy*k + sx of listed pixel j = (r, c) is the direction rtx_ray_directions gives pixel
+ *     (row k*r + sy, column k*c + sx) of the sample scene: the same scene and camera position with a
+ *     (k*width) x (k*height) camera (endpoint fix of the last column and row included). The rays are
+ *     traced by rtx_trace_rays from the shared camera origin, as RTX_OUT_F64_SOA, with the render's
+ *     bounce cap; its status word is checked as after any render.
+ *  4. Output. A flagged pixel is rtx_resolve_samples' value of its k*k samples: each clipped, added
+ *     to 0.0 in ray order (top to bottom, left to right), divided once by k*k. An unflagged pixel is
+ *     clip01(B[p]) (rtx_resolve_samples with k = 1 on the base frame, written before
+ *     rtx_resolve_scatter overwrites the flagged pixels). RTX_OUT_F32_SOA is that value rounded
+ *     once, RTX_OUT_U8_HWC (uint8)(255 * value); every output lies in [0, 1].
+ *  Known approximation: the base sample of pixel c sits at linspace(.., width)[c], which is not the
+ *  centre of its k x k block of linspace(.., k*width).
+ * All three entry points are asynchronous on `stream`, never allocate and never synchronise, and
+ * return RTX_E_ARG before any HIP call for a null pointer, a non-positive width or height (or
+ * width*height >= 2^31), k outside 1..8, an unknown out_kind, a negative or NaN contrast, a negative
+ * n_flagged, or n_flagged*k*k >= 2^31. n_flagged == 0 returns RTX_OK without a launch (pixels_i32 may
+ * then be NULL).
+ * rtx_edge_mask: color_f64 double [3][width*height] (B), id / hits int32 [width*height], lit uint8
+ *   [width*height]; mask_out uint8 [width*height], 1 = flagged.
+ * rtx_sample_dirs: sample_scene is the packed sample scene (its camera words are read, nothing else);
+ *   pixels_i32 int32 [n_flagged] pixel indices r*width + c; dirs_out double [3][n_flagged*k*k]. An
+ *   index outside the frame gives a zero direction.
+ * rtx_resolve_scatter: samples_f64 double [3][n_flagged*k*k] in the ray order above; writes pixel
+ *   pixels_i32[j] of `out` (a whole width x height frame as out_kind says) for every j and nothing
+ *   else. The listed pixels must be distinct; an index outside the frame is skipped. */
+int rtx_edge_mask(const double* color_f64, const int32_t* id, const int32_t* hits, const uint8_t* lit,
+                  int width, int height, double contrast, uint8_t* mask_out, void* stream);
+int rtx_sample_dirs(const double* sample_scene, int k, int width, int height, const int32_t* pixels_i32,
+                    int n_flagged, double* dirs_out, void* stream);
+int rtx_resolve_scatter(const double* samples_f64, int k, const int32_t* pixels_i32, int n_flagged,
+                        int width, int height, void* out, int out_kind, void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

@@ -14,6 +14,7 @@ SRC = PKG / "csrc" / "rtx_kernels.hip"
 SMALL_SRC = PKG / "csrc" / "rtx_small.hip"  # includes SRC's device code
 TILES_SRC = PKG / "csrc" / "rtx_tiles.hip"  # host code: the row-tiled multi-GPU frame (RCCL at run time)
 AOV_SRC = PKG / "csrc" / "rtx_aov.hip"  # includes SRC's device code: k_primary_aovs and its entry points
+ADAPTIVE_SRC = PKG / "csrc" / "rtx_adaptive.hip"  # includes SRC's device code: adaptive anti-aliasing
 HDR = REPO / "include" / "rtx_hip.h"
 LIB = PKG / "librtx_hip.so"
 OPS_SRC = PKG / "csrc" / "rt_ops.cpp"
@@ -44,7 +45,7 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    return any(p.stat().st_mtime > t for p in (SRC, SMALL_SRC, TILES_SRC, AOV_SRC, HDR, Path(__file__)))
+    return any(p.stat().st_mtime > t for p in (SRC, SMALL_SRC, TILES_SRC, AOV_SRC, ADAPTIVE_SRC, HDR, Path(__file__)))
 
 
 OBJ_CACHE = PKG / ".objcache"  # compiled units by content hash (a one-unit change rebuilds one unit)
@@ -71,11 +72,11 @@ def _unit_key(src: Path, flags) -> str:
 
 
 def compile_units(out: Path, main_src: Path, small_src: Path | None, extra_flags=(), verbose: bool = False,
-                  small_flags=None, aov_src: Path | None = None) -> None:
+                  small_flags=None, aov_src: Path | None = None, adaptive_src: Path | None = None) -> None:
     """Compile the library's translation units to objects (in parallel) and link ``out``: main_src
     with HIPCC_FLAGS, small_src (None: a single-unit source) with SMALL_FLAGS (or small_flags) added,
     aov_src (the render-pass unit, which includes main_src's device code like small_src; None: a
-    revision without it) with HIPCC_FLAGS."""
+    revision without it) and adaptive_src (the adaptive anti-aliasing unit, likewise) with HIPCC_FLAGS."""
     import tempfile
 
     sf = list(SMALL_FLAGS if small_flags is None else small_flags)
@@ -84,6 +85,8 @@ def compile_units(out: Path, main_src: Path, small_src: Path | None, extra_flags
         units.append((TILES_SRC, []))
     if aov_src is not None:
         units.append((aov_src, []))
+    if adaptive_src is not None:
+        units.append((adaptive_src, []))
     objs, procs = [], []
     # objects in a directory of this call's own: concurrent builds (several ranks importing on a
     # fresh checkout) cannot overwrite or delete each other's objects before the link
@@ -127,7 +130,7 @@ def build_library(force: bool = False, extra_flags=(), out: Path | None = None, 
         return out
     tmp = out.with_suffix(f".so.tmp{os.getpid()}")  # per process: concurrent builds each rename a whole file
     try:
-        compile_units(tmp, SRC, SMALL_SRC, extra_flags, verbose, aov_src=AOV_SRC)
+        compile_units(tmp, SRC, SMALL_SRC, extra_flags, verbose, aov_src=AOV_SRC, adaptive_src=ADAPTIVE_SRC)
         os.replace(tmp, out)
     finally:
         tmp.unlink(missing_ok=True)

@@ -17,6 +17,10 @@
 //                     <- no counterpart: the primary hit's intermediates as render passes (depth, id,
 //                        hits, position, normal, albedo, lit; rtx_primary_aovs), for a row tile of the
 //                        camera's frame or for explicit rays
+//   rt::edge_mask, rt::sample_dirs, rt::resolve_scatter
+//                     <- no counterpart: adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True);
+//                        rtx_edge_mask, rtx_sample_dirs, rtx_resolve_scatter), with the tensor-size checks
+//                        the bare-pointer C ABI cannot make
 //   rt::status        <- reads and clears the workspace's sticky RTX_ST_* flags
 //   rt::comm_unique_id, rt::comm_init, rt::comm_destroy, rt::tiles_create, rt::tiles_submit,
 //   rt::tiles_finish, rt::tiles_destroy
@@ -475,6 +479,107 @@ std::vector<at::Tensor> primary_aovs_rays(const at::Tensor& scene, int64_t n_sph
   return out;
 }
 
+// ---- adaptive anti-aliasing (rtx_edge_mask, rtx_sample_dirs, rtx_resolve_scatter) ---------------
+// The C ABI takes bare pointers: the tensor sizes are checked here. Shared by the kernels and their
+// Meta forms.
+void check_frame(int64_t width, int64_t height) {
+  TORCH_CHECK(width > 0 && height > 0 && (double)width * (double)height < 2147483648.0,
+              "bad frame geometry (width ", width, ", height ", height, "): positive, width*height below 2^31");
+}
+
+void check_edge_inputs(const at::Tensor& color, const at::Tensor& id, const at::Tensor& hits, const at::Tensor& lit,
+                       int64_t width, int64_t height, double contrast) {
+  check_frame(width, height);
+  TORCH_CHECK(contrast >= 0.0, "contrast must be >= 0 (inf: no colour test), got ", contrast);
+  const int64_t n = width * height;
+  TORCH_CHECK(color.scalar_type() == at::kDouble && color.dim() == 2 && color.size(0) == 3 && color.size(1) == n,
+              "color must be ", at::kDouble, " [3, width*height]");
+  TORCH_CHECK(id.scalar_type() == at::kInt && id.dim() == 1 && id.size(0) == n, "id must be ", at::kInt,
+              " [width*height]");
+  TORCH_CHECK(hits.scalar_type() == at::kInt && hits.dim() == 1 && hits.size(0) == n, "hits must be ", at::kInt,
+              " [width*height]");
+  TORCH_CHECK(lit.scalar_type() == at::kByte && lit.dim() == 1 && lit.size(0) == n, "lit must be ", at::kByte,
+              " [width*height]");
+}
+
+at::Tensor edge_mask(const at::Tensor& color, const at::Tensor& id, const at::Tensor& hits, const at::Tensor& lit,
+                     int64_t width, int64_t height, double contrast) {
+  check_gpu(color, "color", at::kDouble);
+  check_gpu(id, "id", at::kInt);
+  check_gpu(hits, "hits", at::kInt);
+  check_gpu(lit, "lit", at::kByte);
+  check_same_device(color, id, "id");
+  check_same_device(color, hits, "hits");
+  check_same_device(color, lit, "lit");
+  check_edge_inputs(color, id, hits, lit, width, height, contrast);
+  const at::OptionalDeviceGuard guard(at::device_of(color));
+  at::Tensor mask = at::empty({width * height}, color.options().dtype(at::kByte));
+  check_rc(rtx_edge_mask(color.data_ptr<double>(), id.data_ptr<int32_t>(), hits.data_ptr<int32_t>(),
+                         lit.data_ptr<uint8_t>(), (int)width, (int)height, contrast, mask.data_ptr<uint8_t>(),
+                         stream_of(color)),
+           "rtx_edge_mask");
+  return mask;
+}
+
+// pixels int32 [n_flagged]; returns n_flagged
+int64_t check_pixels(const at::Tensor& pixels, int64_t k, int64_t width, int64_t height) {
+  TORCH_CHECK(k >= 1 && k <= 8, "k (samples per pixel side) must be in 1..8, got ", k);
+  check_frame(width, height);
+  TORCH_CHECK(pixels.scalar_type() == at::kInt && pixels.dim() == 1, "pixels must be ", at::kInt, " [n_flagged]");
+  TORCH_CHECK((double)pixels.size(0) * (double)(k * k) < 2147483648.0, "n_flagged*k*k must stay below 2^31");
+  return pixels.size(0);
+}
+
+at::Tensor sample_dirs(const at::Tensor& sample_scene, int64_t k, int64_t width, int64_t height,
+                       const at::Tensor& pixels) {
+  check_gpu(sample_scene, "sample_scene", at::kDouble);
+  check_gpu(pixels, "pixels", at::kInt);
+  check_same_device(sample_scene, pixels, "pixels");
+  TORCH_CHECK(sample_scene.dim() == 1 && sample_scene.numel() >= RTX_HDR_WORDS,
+              "sample_scene must be a 1-D packed scene (at least its header)");
+  const int64_t nf = check_pixels(pixels, k, width, height);
+  const at::OptionalDeviceGuard guard(at::device_of(sample_scene));
+  at::Tensor dirs = at::empty({3, nf * k * k}, sample_scene.options());
+  if (nf == 0) return dirs;  // (an empty tensor's pointer may be null)
+  check_rc(rtx_sample_dirs(sample_scene.data_ptr<double>(), (int)k, (int)width, (int)height,
+                           pixels.data_ptr<int32_t>(), (int)nf, dirs.data_ptr<double>(), stream_of(sample_scene)),
+           "rtx_sample_dirs");
+  return dirs;
+}
+
+void check_scatter(const at::Tensor& samples, int64_t k, const at::Tensor& pixels, int64_t width, int64_t height,
+                   const at::Tensor& out, int64_t out_kind) {
+  const int64_t nf = check_pixels(pixels, k, width, height);
+  TORCH_CHECK(samples.scalar_type() == at::kDouble && samples.dim() == 2 && samples.size(0) == 3 &&
+                  samples.size(1) == nf * k * k,
+              "samples must be ", at::kDouble, " [3, n_flagged*k*k]");
+  const int64_t n = width * height;
+  if (out_kind == RTX_OUT_U8_HWC) {
+    TORCH_CHECK(out.scalar_type() == at::kByte && out.numel() == 3 * n, "out must be ", at::kByte,
+                " [height, width, 3] for out_kind 2");
+  } else {
+    TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA, "bad out_kind ", out_kind);
+    const at::ScalarType want = out_kind == RTX_OUT_F32_SOA ? at::kFloat : at::kDouble;
+    TORCH_CHECK(out.scalar_type() == want && out.dim() == 2 && out.size(0) == 3 && out.size(1) == n, "out must be ",
+                want, " [3, width*height] for out_kind ", out_kind);
+  }
+}
+
+void resolve_scatter(const at::Tensor& samples, int64_t k, const at::Tensor& pixels, int64_t width, int64_t height,
+                     at::Tensor& out, int64_t out_kind) {
+  check_gpu(samples, "samples", at::kDouble);
+  check_gpu(pixels, "pixels", at::kInt);
+  TORCH_CHECK(on_gpu(out) && out.is_contiguous(), "out must be a contiguous GPU tensor");
+  check_same_device(samples, pixels, "pixels");
+  check_same_device(samples, out, "out");
+  check_scatter(samples, k, pixels, width, height, out, out_kind);
+  if (pixels.size(0) == 0) return;
+  const at::OptionalDeviceGuard guard(at::device_of(samples));
+  check_rc(rtx_resolve_scatter(samples.data_ptr<double>(), (int)k, pixels.data_ptr<int32_t>(), (int)pixels.size(0),
+                               (int)width, (int)height, out.data_ptr(), (int)out_kind, stream_of(samples)),
+           "rtx_resolve_scatter");
+}
+
 int64_t status(at::Tensor& workspace) {
   check_gpu(workspace, "workspace", at::kByte);
   TORCH_CHECK(workspace.numel() >= RTX_WS_HDR_BYTES, "workspace shorter than its header");
@@ -649,6 +754,24 @@ std::vector<at::Tensor> primary_aovs_rays_meta(const at::Tensor& scene, int64_t 
   return new_aovs(scene, dirs.size(1), passes);
 }
 
+at::Tensor edge_mask_meta(const at::Tensor& color, const at::Tensor& id, const at::Tensor& hits,
+                          const at::Tensor& lit, int64_t width, int64_t height, double contrast) {
+  check_edge_inputs(color, id, hits, lit, width, height, contrast);
+  return at::empty({width * height}, color.options().dtype(at::kByte));
+}
+
+at::Tensor sample_dirs_meta(const at::Tensor& sample_scene, int64_t k, int64_t width, int64_t height,
+                            const at::Tensor& pixels) {
+  TORCH_CHECK(sample_scene.dim() == 1 && sample_scene.numel() >= RTX_HDR_WORDS,
+              "sample_scene must be a 1-D packed scene (at least its header)");
+  return at::empty({3, check_pixels(pixels, k, width, height) * k * k}, sample_scene.options().dtype(at::kDouble));
+}
+
+void resolve_scatter_meta(const at::Tensor& samples, int64_t k, const at::Tensor& pixels, int64_t width,
+                          int64_t height, at::Tensor& out, int64_t out_kind) {
+  check_scatter(samples, k, pixels, width, height, out, out_kind);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rt, m) {
@@ -670,6 +793,10 @@ TORCH_LIBRARY(rt, m) {
         "int part_run, int passes, bool check=True) -> Tensor[]");
   m.def("primary_aovs_rays(Tensor scene, int n_spheres, Tensor origins, Tensor dirs, int passes, "
         "bool check=True) -> Tensor[]");
+  m.def("edge_mask(Tensor color, Tensor id, Tensor hits, Tensor lit, int width, int height, float contrast) -> Tensor");
+  m.def("sample_dirs(Tensor sample_scene, int k, int width, int height, Tensor pixels) -> Tensor");
+  m.def("resolve_scatter(Tensor samples, int k, Tensor pixels, int width, int height, Tensor(a!) out, "
+        "int out_kind) -> ()");
   m.def("status(Tensor(a!) workspace) -> int");
   m.def("workspace_bytes(int n_rays, int max_bounces) -> int", &workspace_bytes);
   // the row-tiled multi-GPU frame (one native call per frame and rank; handles are int64)
@@ -698,6 +825,9 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("resolve_samples", &resolve_samples);
   m.impl("primary_aovs", &primary_aovs);
   m.impl("primary_aovs_rays", &primary_aovs_rays);
+  m.impl("edge_mask", &edge_mask);
+  m.impl("sample_dirs", &sample_dirs);
+  m.impl("resolve_scatter", &resolve_scatter);
   m.impl("status", &status);
 }
 
@@ -714,6 +844,9 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("resolve_samples", &resolve_samples);
   m.impl("primary_aovs", &primary_aovs);
   m.impl("primary_aovs_rays", &primary_aovs_rays);
+  m.impl("edge_mask", &edge_mask);
+  m.impl("sample_dirs", &sample_dirs);
+  m.impl("resolve_scatter", &resolve_scatter);
   m.impl("status", &status);
 }
 
@@ -728,4 +861,7 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("resolve_samples", &resolve_samples_meta);
   m.impl("primary_aovs", &primary_aovs_meta);
   m.impl("primary_aovs_rays", &primary_aovs_rays_meta);
+  m.impl("edge_mask", &edge_mask_meta);
+  m.impl("sample_dirs", &sample_dirs_meta);
+  m.impl("resolve_scatter", &resolve_scatter_meta);
 }

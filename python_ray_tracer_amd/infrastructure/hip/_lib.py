@@ -106,6 +106,9 @@ EXPORTS = (
     "rtx_last_launches",
     "rtx_primary_aovs",
     "rtx_primary_aovs_rays",
+    "rtx_edge_mask",
+    "rtx_sample_dirs",
+    "rtx_resolve_scatter",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -169,6 +172,10 @@ _SIGS = {
                                 _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "rtx_primary_aovs_rays": (_i32, [_c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p,
                                      _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "rtx_edge_mask": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, ctypes.c_double, _c_void_p,
+                             _c_void_p]),
+    "rtx_sample_dirs": (_i32, [_c_void_p, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p]),
+    "rtx_resolve_scatter": (_i32, [_c_void_p, _i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p]),
 }
 
 _lib = None

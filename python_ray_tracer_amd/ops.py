@@ -41,6 +41,16 @@ that device's current HIP stream and returns a new tensor):
   float64 [n], 2 id int32 [n], 4 hits int32 [n], 8 position, 16 normal, 32 albedo float64 [3, n],
   64 lit uint8 [n]; the result is a list with one tensor per set bit, in bit order. A pass that is
   not requested is neither computed nor stored. Need no workspace.
+* ``rt::edge_mask(color, id, hits, lit, width, height, contrast)``, ``rt::sample_dirs(sample_scene,
+  k, width, height, pixels)`` and ``rt::resolve_scatter(samples, k, pixels, width, height, out,
+  out_kind)`` — the three steps of adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True);
+  rtx_edge_mask, rtx_sample_dirs, rtx_resolve_scatter; contract in include/rtx_hip.h): the uint8
+  [width*height] mask of the pixels to refine, from a float64 [3, width*height] frame and its ``id`` /
+  ``hits`` (int32) and ``lit`` (uint8) passes (``contrast`` >= 0, ``inf`` for the geometric test alone);
+  the float64 [3, n*k*k] sample directions of the int32 pixel indices ``pixels`` [n] on the packed
+  sample scene (the same scene with a k*width x k*height camera); and the resolve of float64
+  [3, n*k*k] samples written over the listed pixels of ``out`` ([3, width*height] colour or
+  [height, width, 3] uint8, mutated in place; nothing is returned). Every tensor's size is checked.
 * ``rt::status(workspace)`` — reads and clears the sticky RTX_ST_* flags (1 stack overflow,
   2 deferred-list overflow, 4 bad scene); synchronises.
 * ``rt::workspace_bytes(n_rays, max_bounces)``.
@@ -69,7 +79,8 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "resolve_samples", "primary_aovs", "primary_aovs_rays", "status", "workspace_bytes",
+       "resolve_samples", "primary_aovs", "primary_aovs_rays", "edge_mask", "sample_dirs", "resolve_scatter", "status",
+       "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
        "comm_unique_id", "comm_init", "comm_destroy", "tiles_create", "tiles_submit", "tiles_finish",
        "tiles_destroy")

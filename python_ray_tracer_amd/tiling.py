@@ -78,6 +78,40 @@ def check_sample_count(k: int, width: int, rows: int, frames: int = 1) -> int:
     return n
 
 
+def check_adaptive(adaptive, samples: int, contrast):
+    """The arguments of an adaptive render (HipRenderer(samples=k, adaptive=True, contrast=c)) as
+    (adaptive, contrast): ``adaptive`` a bool that needs samples >= 2; ``contrast`` None (no colour
+    test: +inf) or a finite number >= 0. ValueError otherwise."""
+    if not isinstance(adaptive, (bool, np.bool_)):
+        raise ValueError(f"adaptive must be a bool, got {adaptive!r}")
+    if adaptive and samples < 2:
+        raise ValueError(f"adaptive=True refines edge pixels with samples x samples rays: it needs samples >= 2, "
+                         f"got samples={samples}")
+    if contrast is None:
+        return bool(adaptive), float("inf")
+    if isinstance(contrast, bool) or not isinstance(contrast, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(contrast) or contrast < 0:
+        raise ValueError(f"contrast must be None (adaptive: the geometric test alone) or a finite number >= 0, "
+                         f"got {contrast!r}")
+    return bool(adaptive), float(contrast)
+
+
+def check_adaptive_count(k: int, width: int, height: int, flagged: int | None = None) -> int:
+    """Sample rays of an adaptive render, flagged*k*k (``flagged=None``: before the mask is known,
+    the frame alone); ValueError where rtx_edge_mask / rtx_sample_dirs / rtx_resolve_scatter refuse:
+    width*height or flagged*k*k at SAMPLE_LIMIT (2^31) and beyond."""
+    n = int(width) * int(height)
+    if n >= SAMPLE_LIMIT:
+        raise ValueError(f"adaptive: {width}x{height} = {n} pixels, the edge mask takes fewer than 2^31")
+    if flagged is None:
+        return 0
+    rays = int(flagged) * int(k) * int(k)
+    if not 0 <= int(flagged) <= n or rays >= SAMPLE_LIMIT:
+        raise ValueError(f"adaptive: {flagged} flagged pixels of {n} x {k}x{k} samples = {rays} sample rays, "
+                         f"the resolve takes fewer than 2^31; lower samples or raise contrast")
+    return rays
+
+
 def runs(world: int, root_run: int = 1, run: int = 1):
     """(n_parts, [(first part, run) per rank]) of the shares: rank 0 renders parts [0, root_run),
     rank i >= 1 parts [root_run + (i - 1) run, root_run + i run)."""

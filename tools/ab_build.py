@@ -86,21 +86,24 @@ def main():
         small.write_text(small_src.replace('#include "rtx_kernels.hip"', f'#include "{tmp.name}"'))
     # ... and the render-pass unit (rtx_aov.hip, which includes the kernel file the same way), when the
     # revision has one: _lib.load binds its entry points
-    aov = None
+    # and the adaptive anti-aliasing unit (rtx_adaptive.hip), the same way
+    extra = {}
     if small is not None:
-        shown = (subprocess.run(["git", "show", f"{a.rev}:{_build.AOV_SRC.relative_to(REPO)}"], cwd=REPO,
-                                capture_output=True, text=True) if a.rev else None)
-        aov_src = _build.AOV_SRC.read_text() if shown is None else shown.stdout if shown.returncode == 0 else None
-        if aov_src is not None:
-            aov = _build.SRC.with_name(f"_ab_{Path(a.out).stem}_aov.hip")
-            aov.write_text(aov_src.replace('#include "rtx_kernels.hip"', f'#include "{tmp.name}"'))
+        for tag, unit_src in (("aov", _build.AOV_SRC), ("adaptive", _build.ADAPTIVE_SRC)):
+            shown = (subprocess.run(["git", "show", f"{a.rev}:{unit_src.relative_to(REPO)}"], cwd=REPO,
+                                    capture_output=True, text=True) if a.rev else None)
+            text = unit_src.read_text() if shown is None else shown.stdout if shown.returncode == 0 else None
+            if text is not None:
+                extra[tag] = _build.SRC.with_name(f"_ab_{Path(a.out).stem}_{tag}.hip")
+                extra[tag].write_text(text.replace('#include "rtx_kernels.hip"', f'#include "{tmp.name}"'))
     try:
         out = Path(a.out).resolve()
         out.parent.mkdir(parents=True, exist_ok=True)
-        _build.compile_units(out, tmp, small, a.flag, small_flags=a.small_flag, aov_src=aov)
+        _build.compile_units(out, tmp, small, a.flag, small_flags=a.small_flag, aov_src=extra.get("aov"),
+                             adaptive_src=extra.get("adaptive"))
     finally:
         tmp.unlink(missing_ok=True)
-        for unit in (small, aov):
+        for unit in (small, *extra.values()):
             if unit is not None:
                 unit.unlink(missing_ok=True)
     print(out)
