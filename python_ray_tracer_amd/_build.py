@@ -10,11 +10,8 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
 REPO = PKG.parent
-SRC = PKG / "csrc" / "rtx_kernels.hip"
-SMALL_SRC = PKG / "csrc" / "rtx_small.hip"  # includes SRC's device code
-TILES_SRC = PKG / "csrc" / "rtx_tiles.hip"  # host code: the row-tiled multi-GPU frame (RCCL at run time)
-AOV_SRC = PKG / "csrc" / "rtx_aov.hip"  # includes SRC's device code: k_primary_aovs and its entry points
-ADAPTIVE_SRC = PKG / "csrc" / "rtx_adaptive.hip"  # includes SRC's device code: adaptive anti-aliasing
+CSRC = PKG / "csrc"  # every *.hip here is a translation unit of the library; the *.h are what they share
+DEVICE_HDR = CSRC / "rtx_device.h"  # the device text of the render path (tuning constants, k_render_fast)
 HDR = REPO / "include" / "rtx_hip.h"
 LIB = PKG / "librtx_hip.so"
 OPS_SRC = PKG / "csrc" / "rt_ops.cpp"
@@ -27,11 +24,17 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
                # MachineLICM hoists the ocml sin polynomial constants out of the bounce loop into VGPRs,
                # which then spill at 128 VGPRs; A/B (profiles/r1_ab_variants.txt): faster on every config
                "-mllvm", "-disable-machine-licm"]
-# rtx_small.hip only (the TREE = false kernels). Round 3 built them with the max-ilp machine
-# scheduler (profiles/r3_ab_variants.txt: C2 -0.5..-0.9%, C1 -2.4%); with the forward fold of round 5
-# the default scheduler is the faster one (A/B r5i: C2 -0.8%, C1 -0.9%, C2main -0.4%). The unit
-# stays separate so that its flags can differ from the culled kernels'.
+# Flags of one unit, added to HIPCC_FLAGS, by the unit's stem. The units are separate so that they
+# compile in parallel and so that an A/B can give one of them flags of its own (tools/ab_build.py
+# --small-flag). None has any: rtx_small.hip (the TREE = false kernels) is faster with the default
+# machine scheduler than with max-ilp (A/B r5i: C2 -0.8%, C1 -0.9%, C2main -0.4%).
 SMALL_FLAGS: list = []
+UNIT_FLAGS = {"rtx_small": SMALL_FLAGS}
+
+
+def library_units(csrc: Path = CSRC, unit_flags=UNIT_FLAGS) -> list:
+    """The library's translation units: every *.hip of csrc, each with its own extra flags."""
+    return [(src, list(unit_flags.get(src.stem, []))) for src in sorted(csrc.glob("*.hip"))]
 
 
 def hipcc() -> str:
@@ -45,7 +48,8 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    return any(p.stat().st_mtime > t for p in (SRC, SMALL_SRC, TILES_SRC, AOV_SRC, ADAPTIVE_SRC, HDR, Path(__file__)))
+    sources = [*CSRC.iterdir(), *HDR.parent.iterdir(), Path(__file__)]
+    return any(p.stat().st_mtime > t for p in sources if p.is_file())
 
 
 OBJ_CACHE = PKG / ".objcache"  # compiled units by content hash (a one-unit change rebuilds one unit)
@@ -71,22 +75,11 @@ def _unit_key(src: Path, flags) -> str:
     return h.hexdigest()[:32]
 
 
-def compile_units(out: Path, main_src: Path, small_src: Path | None, extra_flags=(), verbose: bool = False,
-                  small_flags=None, aov_src: Path | None = None, adaptive_src: Path | None = None) -> None:
-    """Compile the library's translation units to objects (in parallel) and link ``out``: main_src
-    with HIPCC_FLAGS, small_src (None: a single-unit source) with SMALL_FLAGS (or small_flags) added,
-    aov_src (the render-pass unit, which includes main_src's device code like small_src; None: a
-    revision without it) and adaptive_src (the adaptive anti-aliasing unit, likewise) with HIPCC_FLAGS."""
+def compile_units(out: Path, units, extra_flags=(), verbose: bool = False) -> None:
+    """Compile translation units, a list of (path, flags), to objects (in parallel), each with
+    HIPCC_FLAGS, its own flags and extra_flags, and link ``out``."""
     import tempfile
 
-    sf = list(SMALL_FLAGS if small_flags is None else small_flags)
-    units = [(main_src, [])] + ([(small_src, sf)] if small_src is not None else [])
-    if small_src is not None and TILES_SRC.exists():  # (single-unit revisions of the A/B tool build alone)
-        units.append((TILES_SRC, []))
-    if aov_src is not None:
-        units.append((aov_src, []))
-    if adaptive_src is not None:
-        units.append((adaptive_src, []))
     objs, procs = [], []
     # objects in a directory of this call's own: concurrent builds (several ranks importing on a
     # fresh checkout) cannot overwrite or delete each other's objects before the link
@@ -130,7 +123,7 @@ def build_library(force: bool = False, extra_flags=(), out: Path | None = None, 
         return out
     tmp = out.with_suffix(f".so.tmp{os.getpid()}")  # per process: concurrent builds each rename a whole file
     try:
-        compile_units(tmp, SRC, SMALL_SRC, extra_flags, verbose, aov_src=AOV_SRC, adaptive_src=ADAPTIVE_SRC)
+        compile_units(tmp, library_units(), extra_flags, verbose)
         os.replace(tmp, out)
     finally:
         tmp.unlink(missing_ok=True)

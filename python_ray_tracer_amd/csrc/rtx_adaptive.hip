@@ -5,14 +5,11 @@
 //   k_sample_dirs     the k x k sample rays of the listed pixels: camera_dir on the sample scene
 //   k_resolve_scatter the resolve of each listed pixel's samples, written over that
 //                     pixel of the frame
-// A translation unit of its own, like rtx_aov.hip: the device code is rtx_kernels.hip's, included up
-// to its host section, so the render kernels compile from untouched text with untouched flags, and
-// camera_dir / clip01 / quant_u8 here are the render path's own.
-#define RTX_DEVICE_CODE_ONLY
-#include "rtx_kernels.hip"
-
-// rtx_kernels.hip's error message (rtx_last_error)
-__attribute__((visibility("hidden"))) int rtx_set_error(int code, const char* msg);
+// A translation unit of its own, like rtx_aov.hip, over the shared device text (rtx_device.h): the
+// render kernels compile from untouched text with untouched flags, and camera_dir / clip01 /
+// quant_u8 here are the render path's own.
+#include "rtx_device.h"
+#include "rtx_internal.h"
 
 namespace {
 
@@ -189,18 +186,6 @@ __global__ __launch_bounds__(kBlock) void k_resolve_scatter(const double* __rest
   }
 }
 
-int adaptive_fail(const char* msg) { return rtx_set_error(RTX_E_ARG, msg); }
-
-int adaptive_launched(const char* kernel) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", kernel, hipGetErrorString(e));
-    return rtx_set_error(RTX_E_LAUNCH, msg);
-  }
-  return RTX_OK;
-}
-
 constexpr int64_t kIndexLimit = (int64_t)1 << 31;  // pixel and sample-ray indices are 32-bit
 
 bool frame_fits(int width, int height) { return (int64_t)width * height < kIndexLimit; }
@@ -213,49 +198,52 @@ extern "C" {
 
 int rtx_edge_mask(const double* color_f64, const int32_t* id, const int32_t* hits, const uint8_t* lit, int width,
                   int height, double contrast, uint8_t* mask_out, void* stream) {
-  if (!color_f64 || !id || !hits || !lit || !mask_out) return adaptive_fail("rtx_edge_mask: null pointer argument");
+  if (!color_f64 || !id || !hits || !lit || !mask_out)
+    return rtx_fail(RTX_E_ARG, "rtx_edge_mask: null pointer argument");
   if (width <= 0 || height <= 0 || !frame_fits(width, height))
-    return adaptive_fail("rtx_edge_mask: bad frame geometry (width and height positive, width*height below 2^31)");
-  if (!(contrast >= 0.0)) return adaptive_fail("rtx_edge_mask: contrast must be >= 0 (+inf: no colour test), not NaN");
+    return rtx_fail(RTX_E_ARG, "rtx_edge_mask: bad frame geometry (width and height positive, width*height below 2^31)");
+  if (!(contrast >= 0.0))
+    return rtx_fail(RTX_E_ARG, "rtx_edge_mask: contrast must be >= 0 (+inf: no colour test), not NaN");
   const int64_t tiles = (((int64_t)width + kMaskW - 1) / kMaskW) * (((int64_t)height + kMaskH - 1) / kMaskH);
-  if (tiles >= kIndexLimit) return adaptive_fail("rtx_edge_mask: bad frame geometry (too many tiles for one launch)");
+  if (tiles >= kIndexLimit)
+    return rtx_fail(RTX_E_ARG, "rtx_edge_mask: bad frame geometry (too many tiles for one launch)");
   hipLaunchKernelGGL(k_edge_mask, dim3((unsigned)tiles), dim3(kBlock), 0, (hipStream_t)stream, color_f64,
                      (const int*)id, (const int*)hits, lit, width, height, contrast, mask_out);
-  return adaptive_launched("k_edge_mask");
+  return rtx_launched("k_edge_mask");
 }
 
 int rtx_sample_dirs(const double* sample_scene, int k, int width, int height, const int32_t* pixels_i32,
                     int n_flagged, double* dirs_out, void* stream) {
   if (!sample_scene || !dirs_out || (!pixels_i32 && n_flagged != 0))
-    return adaptive_fail("rtx_sample_dirs: null pointer argument");
-  if (k < 1 || k > 8) return adaptive_fail("rtx_sample_dirs: samples per pixel side must be in 1..8");
+    return rtx_fail(RTX_E_ARG, "rtx_sample_dirs: null pointer argument");
+  if (k < 1 || k > 8) return rtx_fail(RTX_E_ARG, "rtx_sample_dirs: samples per pixel side must be in 1..8");
   if (width <= 0 || height <= 0 || n_flagged < 0 || !frame_fits(width, height) ||
       (int64_t)k * width >= kIndexLimit || (int64_t)k * height >= kIndexLimit)
-    return adaptive_fail("rtx_sample_dirs: bad frame geometry or a negative pixel count");
+    return rtx_fail(RTX_E_ARG, "rtx_sample_dirs: bad frame geometry or a negative pixel count");
   if ((int64_t)n_flagged * k * k >= kIndexLimit)
-    return adaptive_fail("rtx_sample_dirs: n_flagged*k*k must stay below 2^31 sample rays");
+    return rtx_fail(RTX_E_ARG, "rtx_sample_dirs: n_flagged*k*k must stay below 2^31 sample rays");
   if (n_flagged == 0) return RTX_OK;
   const int n_rays = n_flagged * k * k;
   hipLaunchKernelGGL(k_sample_dirs, dim3(blocks_for(n_rays)), dim3(kBlock), 0, (hipStream_t)stream, sample_scene, k,
                      width, height, (const int*)pixels_i32, n_rays, dirs_out);
-  return adaptive_launched("k_sample_dirs");
+  return rtx_launched("k_sample_dirs");
 }
 
 int rtx_resolve_scatter(const double* samples_f64, int k, const int32_t* pixels_i32, int n_flagged, int width,
                         int height, void* out, int out_kind, void* stream) {
   if (!samples_f64 || !out || (!pixels_i32 && n_flagged != 0))
-    return adaptive_fail("rtx_resolve_scatter: null pointer argument");
-  if (k < 1 || k > 8) return adaptive_fail("rtx_resolve_scatter: samples per pixel side must be in 1..8");
+    return rtx_fail(RTX_E_ARG, "rtx_resolve_scatter: null pointer argument");
+  if (k < 1 || k > 8) return rtx_fail(RTX_E_ARG, "rtx_resolve_scatter: samples per pixel side must be in 1..8");
   if (width <= 0 || height <= 0 || n_flagged < 0 || !frame_fits(width, height))
-    return adaptive_fail("rtx_resolve_scatter: bad frame geometry or a negative pixel count");
+    return rtx_fail(RTX_E_ARG, "rtx_resolve_scatter: bad frame geometry or a negative pixel count");
   if (out_kind != RTX_OUT_F32_SOA && out_kind != RTX_OUT_F64_SOA && out_kind != RTX_OUT_U8_HWC)
-    return adaptive_fail("rtx_resolve_scatter: bad out_kind");
+    return rtx_fail(RTX_E_ARG, "rtx_resolve_scatter: bad out_kind");
   if ((int64_t)n_flagged * k * k >= kIndexLimit)
-    return adaptive_fail("rtx_resolve_scatter: n_flagged*k*k must stay below 2^31 samples per plane");
+    return rtx_fail(RTX_E_ARG, "rtx_resolve_scatter: n_flagged*k*k must stay below 2^31 samples per plane");
   if (n_flagged == 0) return RTX_OK;
   hipLaunchKernelGGL(k_resolve_scatter, dim3(blocks_for(n_flagged)), dim3(kBlock), 0, (hipStream_t)stream,
                      samples_f64, k, (const int*)pixels_i32, n_flagged, width, height, out, out_kind);
-  return adaptive_launched("k_resolve_scatter");
+  return rtx_launched("k_resolve_scatter");
 }
 
 }  // extern "C"

@@ -3,13 +3,10 @@
 // ray of every pixel (or of every explicit ray). Each value is an intermediate of the reference's own
 // arithmetic (base.py:97-103, shader.py:73-84, Texture.get_color) that the render kernels compute
 // and discard; here they are written out, by one kernel of its own beside the render kernels, in a
-// translation unit of its own: the device code is rtx_kernels.hip's, included up to its host
-// section, so k_render_fast / k_render_general compile from untouched text with untouched flags.
-#define RTX_DEVICE_CODE_ONLY
-#include "rtx_kernels.hip"
-
-// rtx_kernels.hip's error message (rtx_last_error)
-__attribute__((visibility("hidden"))) int rtx_set_error(int code, const char* msg);
+// translation unit of its own over the shared device text (rtx_device.h), so the render kernels
+// compile from untouched text with untouched flags.
+#include "rtx_device.h"
+#include "rtx_internal.h"
 
 namespace {
 
@@ -151,20 +148,12 @@ __global__ __launch_bounds__(kBlock) void k_primary_aovs(Params p, AovOut o) {
   }
 }
 
-int aov_fail(const char* msg) { return rtx_set_error(RTX_E_ARG, msg); }
-
 int launch_aovs(const Params& p, double* depth, int32_t* id, int32_t* hits, double* position, double* normal,
                 double* albedo, uint8_t* lit, void* stream) {
   AovOut o{depth, (int*)id, (int*)hits, position, normal, albedo, lit, (uintptr_t)lit % 4 == 0 ? 1 : 0};
   hipLaunchKernelGGL(k_primary_aovs, dim3((unsigned)((p.n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                      (hipStream_t)stream, p, o);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char msg[256];
-    snprintf(msg, sizeof(msg), "k_primary_aovs: %s", hipGetErrorString(e));
-    return rtx_set_error(RTX_E_LAUNCH, msg);
-  }
-  return RTX_OK;
+  return rtx_launched("k_primary_aovs");
 }
 
 }  // namespace
@@ -174,26 +163,14 @@ extern "C" {
 int rtx_primary_aovs(const double* scene, int n_spheres, int width, int height, int row_block, int n_parts, int part,
                      int part_run, int n_local_rows, double* depth, int32_t* id, int32_t* hits, double* position,
                      double* normal, double* albedo, uint8_t* lit, void* stream) {
-  if (!scene) return aov_fail("null scene pointer");
+  if (!scene) return rtx_fail(RTX_E_ARG, "null scene pointer");
   if (!depth && !id && !hits && !position && !normal && !albedo && !lit)
-    return aov_fail("no pass requested: every output pointer is null");
-  if (n_spheres < 1 || n_spheres > RTX_MAX_SPHERES) return aov_fail("n_spheres out of range");
-  if (width <= 0 || height <= 0 || row_block <= 0 || n_parts <= 0 || part < 0 || part_run < 1 ||
-      part_run > n_parts - part || n_local_rows < 0 ||
-      n_local_rows > tile_local_rows(height, row_block, n_parts, part, part_run))
-    return aov_fail("bad frame/tile geometry");
+    return rtx_fail(RTX_E_ARG, "no pass requested: every output pointer is null");
+  if (n_spheres < 1 || n_spheres > RTX_MAX_SPHERES) return rtx_fail(RTX_E_ARG, "n_spheres out of range");
+  if (!tile_geometry_ok(width, height, row_block, n_parts, part, part_run, n_local_rows))
+    return rtx_fail(RTX_E_ARG, "bad frame/tile geometry");
   Params p{};
-  p.scene = scene;
-  p.nsph = n_spheres;
-  p.mode = 0;
-  p.width = width;
-  p.height = height;
-  p.row_block = row_block;
-  p.n_parts = n_parts;
-  p.part = part;
-  p.part_run = part_run;
-  p.n_rows = n_local_rows;
-  p.n = (int64_t)width * n_local_rows;
+  camera_params(p, scene, n_spheres, width, height, row_block, n_parts, part, part_run, n_local_rows);
   if (p.n == 0) return RTX_OK;
   return launch_aovs(p, depth, id, hits, position, normal, albedo, lit, stream);
 }
@@ -201,22 +178,16 @@ int rtx_primary_aovs(const double* scene, int n_spheres, int width, int height, 
 int rtx_primary_aovs_rays(const double* scene, int n_spheres, const double* origins, int64_t origin_stride,
                           const double* dirs, int64_t n, double* depth, int32_t* id, int32_t* hits, double* position,
                           double* normal, double* albedo, uint8_t* lit, void* stream) {
-  if (!scene) return aov_fail("null scene pointer");
-  if (!origins || !dirs) return aov_fail("null ray pointer");
+  if (!scene) return rtx_fail(RTX_E_ARG, "null scene pointer");
+  if (!origins || !dirs) return rtx_fail(RTX_E_ARG, "null ray pointer");
   if (!depth && !id && !hits && !position && !normal && !albedo && !lit)
-    return aov_fail("no pass requested: every output pointer is null");
-  if (n_spheres < 1 || n_spheres > RTX_MAX_SPHERES) return aov_fail("n_spheres out of range");
-  if (n < 0) return aov_fail("negative ray count");
-  if (origin_stride != 0 && origin_stride != n) return aov_fail("origin_stride must be 0 or n");
+    return rtx_fail(RTX_E_ARG, "no pass requested: every output pointer is null");
+  if (n_spheres < 1 || n_spheres > RTX_MAX_SPHERES) return rtx_fail(RTX_E_ARG, "n_spheres out of range");
+  if (n < 0) return rtx_fail(RTX_E_ARG, "negative ray count");
+  if (origin_stride != 0 && origin_stride != n) return rtx_fail(RTX_E_ARG, "origin_stride must be 0 or n");
   if (n == 0) return RTX_OK;
   Params p{};
-  p.scene = scene;
-  p.nsph = n_spheres;
-  p.mode = 1;
-  p.org = origins;
-  p.org_stride = origin_stride;
-  p.dir = dirs;
-  p.n = n;
+  ray_params(p, scene, n_spheres, 1, origins, origin_stride, dirs, n);
   return launch_aovs(p, depth, id, hits, position, normal, albedo, lit, stream);
 }
 

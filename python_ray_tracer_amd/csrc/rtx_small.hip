@@ -1,15 +1,10 @@
 // rtx_small.hip — the k_render_fast instantiations of scenes below kTreeMinSpheres (TP 0: no culling
 // tree, no persistent loop; the README and main.py scenes, BASELINE configs C1/C2), in a translation
-// unit of their own so that they build with the max-ilp machine scheduler (_build.SMALL_FLAGS) while
-// the culled kernels keep the default one (profiles/r3_ab_variants.txt r3x-r3z). The device code is
-// rtx_kernels.hip's, included up to its host section; the launch sites there call rtx_launch_small.
-#define RTX_DEVICE_CODE_ONLY
-#include "rtx_kernels.hip"
-
-// rtx_kernels.hip's launch record (rtx_last_launches)
-__attribute__((visibility("hidden"))) void rtx_note_launch(int B, int lds, int deep, int stats, int tp, int img,
-                                                           int nsph, int waves, dim3 grid, int n_fetch, int ordered,
-                                                           uint32_t lds_bytes);
+// unit of their own: they compile beside the culled kernels of rtx_kernels.hip, not after them, and
+// an A/B can give them flags of their own (_build.SMALL_FLAGS). The launch sites in rtx_kernels.hip
+// call rtx_launch_small.
+#include "rtx_device.h"
+#include "rtx_internal.h"
 
 namespace {
 
@@ -55,9 +50,8 @@ hipError_t go_b(bool stats, bool img, const void* params, dim3 grid, uint32_t ld
 
 }  // namespace
 
-__attribute__((visibility("hidden"))) hipError_t rtx_launch_small(int B, int deep, bool stats, bool img,
-                                                                  const void* params, dim3 grid, uint32_t lds,
-                                                                  hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+hipError_t rtx_launch_small(int B, int deep, bool stats, bool img, const void* params, dim3 grid, uint32_t lds,
+                            hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
   if (deep) {  // 1: an uncapped render's first pass, 2: its continuation pass
     if (B != kDeepLevels) return hipErrorInvalidValue;
     return deep == 2 ? go_b<kDeepLevels, 2>(stats, img, params, grid, lds, s, e0, e1)

@@ -24,10 +24,7 @@
 #include <cstring>
 #include <mutex>
 
-#include "../../include/rtx_hip.h"
-
-// rtx_kernels.hip: the library's thread-local error message
-__attribute__((visibility("hidden"))) int rtx_set_error(int code, const char* msg);
+#include "rtx_internal.h"
 
 namespace {
 
@@ -46,16 +43,8 @@ struct Rccl {
 Rccl g_rccl;
 std::mutex g_rccl_mu;
 
-int err(int code, const char* fmt, const char* a = "", long long b = 0) {
-  char m[512];
-  snprintf(m, sizeof(m), fmt, a, b);
-  return rtx_set_error(code, m);
-}
-
 int nccl_err(const char* what, ncclResult_t r) {
-  char m[512];
-  snprintf(m, sizeof(m), "%s: %s", what, g_rccl.error_string ? g_rccl.error_string(r) : "RCCL error");
-  return rtx_set_error(RTX_E_COMM, m);
+  return rtx_fail(RTX_E_COMM, "%s: %s", what, g_rccl.error_string ? g_rccl.error_string(r) : "RCCL error");
 }
 
 bool rccl_ready() { return g_rccl.send != nullptr; }
@@ -94,14 +83,6 @@ struct Tiles {
   bool used[RTX_TILES_MAX_SLOTS];
 };
 
-int local_rows(int height, int row_block, int n_parts, int p, int run = 1) {  // tiling.n_local_rows
-  const int cycle = row_block * n_parts, own = row_block * run;
-  const int q = height / cycle, rem = height % cycle - p * row_block;
-  return q * own + (rem < 0 ? 0 : rem > own ? own : rem);
-}
-
-int64_t bytes_per_pixel(int kind) { return kind == RTX_OUT_F32_SOA ? 12 : kind == RTX_OUT_F64_SOA ? 24 : 3; }
-
 // RTX_TILES_ROWS: the gather moves every row block of a part on its own, straight into its rows of
 // the root's frame (a uint8 row block is contiguous there), so the root never assembles: per peer,
 // one ncclSend per block of its tile (local rows in order), and at the root one ncclRecv per block
@@ -115,7 +96,7 @@ int gather_rows(Tiles* t, int slot, bool root, uint8_t* frame) {
   const bool sender = t->loop || !root;
   const int dest = t->loop ? 0 : t->root;
   if (sender) {
-    const int n = local_rows(t->height, rb, P, t->rank);
+    const int n = tile_local_rows(t->height, rb, P, t->rank);
     for (int j = 0; j * rb < n && r == ncclSuccess; ++j) {
       const int rows = n - j * rb < rb ? n - j * rb : rb;
       r = g_rccl.send((const uint8_t*)t->send[slot] + (int64_t)j * rb * rowb, (size_t)(rows * rowb), ncclUint8, dest,
@@ -125,7 +106,7 @@ int gather_rows(Tiles* t, int slot, bool root, uint8_t* frame) {
   if (root) {
     for (int p = 0; p < P && r == ncclSuccess; ++p) {
       if (p == t->root && !t->loop) continue;
-      const int n = local_rows(t->height, rb, P, p);
+      const int n = tile_local_rows(t->height, rb, P, p);
       for (int j = 0; j * rb < n && r == ncclSuccess; ++j) {
         const int rows = n - j * rb < rb ? n - j * rb : rb;
         r = g_rccl.recv(frame + (int64_t)(j * P + p) * rb * rowb, (size_t)(rows * rowb), ncclUint8, p, t->comm, t->cs);
@@ -149,7 +130,7 @@ int gather_rows(Tiles* t, int slot, bool root, uint8_t* frame) {
   }
   if (e == hipSuccess && t->timed) e = hipEventRecord(t->a1[slot], t->cs);
   if (e == hipSuccess) e = hipEventRecord(t->done[slot], t->cs);
-  if (e != hipSuccess) return err(RTX_E_LAUNCH, "gather_rows: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return rtx_fail(RTX_E_LAUNCH, "gather_rows: %s", hipGetErrorString(e));
   return RTX_OK;
 }
 
@@ -165,7 +146,7 @@ int rtx_rccl_load(const char* path) {
   if (!h) h = dlopen(path && *path ? path : "librccl.so", RTLD_NOW | RTLD_LOCAL);
   if (!h) {
     const char* why = dlerror();
-    return err(RTX_E_COMM, "cannot load RCCL (%s)", why ? why : "dlopen failed");
+    return rtx_fail(RTX_E_COMM, "cannot load RCCL (%s)", why ? why : "dlopen failed");
   }
   g_rccl = Rccl{};
   g_rccl.lib = h;
@@ -175,15 +156,15 @@ int rtx_rccl_load(const char* path) {
             sym(g_rccl.error_string, "ncclGetErrorString") && sym(g_rccl.send, "ncclSend");
   if (!ok) {
     g_rccl = Rccl{};
-    return err(RTX_E_COMM, "RCCL library lacks a required symbol%s", "");
+    return rtx_fail(RTX_E_COMM, "RCCL library lacks a required symbol");
   }
   sym(g_rccl.comm_init_rank_config, "ncclCommInitRankConfig");
   return RTX_OK;
 }
 
 int rtx_comm_unique_id(void* id_out) {
-  if (!id_out) return err(RTX_E_ARG, "null pointer argument%s", "");
-  if (!rccl_ready()) return err(RTX_E_COMM, "RCCL not loaded (rtx_rccl_load)%s", "");
+  if (!id_out) return rtx_fail(RTX_E_ARG, "null pointer argument");
+  if (!rccl_ready()) return rtx_fail(RTX_E_COMM, "RCCL not loaded (rtx_rccl_load)");
   ncclUniqueId id;
   if (ncclResult_t r = g_rccl.get_unique_id(&id)) return nccl_err("ncclGetUniqueId", r);
   memcpy(id_out, &id, sizeof(id));
@@ -191,14 +172,14 @@ int rtx_comm_unique_id(void* id_out) {
 }
 
 int rtx_comm_init(const void* id, int world, int rank, int max_ctas, void** comm_out) {
-  if (!id || !comm_out) return err(RTX_E_ARG, "null pointer argument%s", "");
-  if (world < 1 || rank < 0 || rank >= world) return err(RTX_E_ARG, "bad world/rank%s (%lld)", "", world);
-  if (!rccl_ready()) return err(RTX_E_COMM, "RCCL not loaded (rtx_rccl_load)%s", "");
+  if (!id || !comm_out) return rtx_fail(RTX_E_ARG, "null pointer argument");
+  if (world < 1 || rank < 0 || rank >= world) return rtx_fail(RTX_E_ARG, "bad world/rank (%d)", world);
+  if (!rccl_ready()) return rtx_fail(RTX_E_COMM, "RCCL not loaded (rtx_rccl_load)");
   ncclUniqueId uid;
   memcpy(&uid, id, sizeof(uid));
   ncclComm_t c = nullptr;
   if (max_ctas > 0) {  // cap the CTAs (blocks) of the communicator's kernels: the gather runs beside a render
-    if (!g_rccl.comm_init_rank_config) return err(RTX_E_COMM, "RCCL lacks ncclCommInitRankConfig%s", "");
+    if (!g_rccl.comm_init_rank_config) return rtx_fail(RTX_E_COMM, "RCCL lacks ncclCommInitRankConfig");
     ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
     cfg.minCTAs = 1;
     cfg.maxCTAs = max_ctas;
@@ -213,7 +194,7 @@ int rtx_comm_init(const void* id, int world, int rank, int max_ctas, void** comm
 
 int rtx_comm_destroy(void* comm) {
   if (!comm) return RTX_OK;
-  if (!rccl_ready()) return err(RTX_E_COMM, "RCCL not loaded%s", "");
+  if (!rccl_ready()) return rtx_fail(RTX_E_COMM, "RCCL not loaded");
   if (ncclResult_t r = g_rccl.comm_destroy((ncclComm_t)comm)) return nccl_err("ncclCommDestroy", r);
   return RTX_OK;
 }
@@ -221,38 +202,39 @@ int rtx_comm_destroy(void* comm) {
 int rtx_tiles_create(void* comm, int world, int rank, int root, int width, int height, int row_block, int out_kind,
                      int slots, void* const* send, void* const* recv, int64_t part_bytes, int root_run, int run,
                      unsigned flags, void** plan_out) {
-  if (!plan_out) return err(RTX_E_ARG, "null plan pointer%s", "");
+  if (!plan_out) return rtx_fail(RTX_E_ARG, "null plan pointer");
   *plan_out = nullptr;
   if (world < 1 || rank < 0 || rank >= world || root < 0 || root >= world)
-    return err(RTX_E_ARG, "bad world/rank/root%s (%lld)", "", world);
-  if (width <= 0 || height <= 0 || row_block <= 0) return err(RTX_E_ARG, "bad frame/tile geometry%s", "");
-  if (out_kind < 0 || out_kind > 2) return err(RTX_E_ARG, "bad out_kind%s %lld", "", out_kind);
-  if (slots < 1 || slots > RTX_TILES_MAX_SLOTS) return err(RTX_E_ARG, "bad slot count%s (%lld)", "", slots);
+    return rtx_fail(RTX_E_ARG, "bad world/rank/root (%d)", world);
+  if (width <= 0 || height <= 0 || row_block <= 0) return rtx_fail(RTX_E_ARG, "bad frame/tile geometry");
+  if (out_kind < 0 || out_kind > 2) return rtx_fail(RTX_E_ARG, "bad out_kind %d", out_kind);
+  if (slots < 1 || slots > RTX_TILES_MAX_SLOTS) return rtx_fail(RTX_E_ARG, "bad slot count (%d)", slots);
   if (flags & ~(unsigned)(RTX_TILES_LOOPBACK | RTX_TILES_ROWS | RTX_TILES_TIMED | RTX_F_RESERVE(0xFFF)))
-    return err(RTX_E_ARG, "unknown flags%s (%lld)", "", (long long)flags);
+    return rtx_fail(RTX_E_ARG, "unknown flags (%lld)", (long long)flags);
   const bool loop = world == 1 && (flags & RTX_TILES_LOOPBACK);
   const bool rows = (flags & RTX_TILES_ROWS) && (world > 1 || loop);
   if (rows && out_kind != RTX_OUT_U8_HWC)
-    return err(RTX_E_ARG, "RTX_TILES_ROWS needs uint8 frames (a row block is contiguous there)%s", "");
+    return rtx_fail(RTX_E_ARG, "RTX_TILES_ROWS needs uint8 frames (a row block is contiguous there)");
   if ((world > 1 || loop) && (!comm || !rccl_ready()))
-    return err(RTX_E_COMM, "world > 1 (or a loopback plan) needs an RCCL communicator%s", "");
+    return rtx_fail(RTX_E_COMM, "world > 1 (or a loopback plan) needs an RCCL communicator");
   if (root_run < 1 || run < 1 || (world == 1 && (root_run != 1 || run != 1)) || (root != 0 && root_run != run))
-    return err(RTX_E_ARG, "bad runs%s (root_run %lld)", "", root_run);
-  if (rows && (root_run != 1 || run != 1)) return err(RTX_E_ARG, "RTX_TILES_ROWS needs runs of one part%s", "");
+    return rtx_fail(RTX_E_ARG, "bad runs (root_run %d)", root_run);
+  if (rows && (root_run != 1 || run != 1)) return rtx_fail(RTX_E_ARG, "RTX_TILES_ROWS needs runs of one part");
   const int np = root_run + (world - 1) * run;
   int rows_max = 0;  // the longest run's tile
   for (int r = 0; r < world; ++r) {
-    const int n = r == 0 ? local_rows(height, row_block, np, 0, root_run)
-                         : local_rows(height, row_block, np, root_run + (r - 1) * run, run);
+    const int n = r == 0 ? tile_local_rows(height, row_block, np, 0, root_run)
+                         : tile_local_rows(height, row_block, np, root_run + (r - 1) * run, run);
     rows_max = n > rows_max ? n : rows_max;
   }
-  if (part_bytes < rows_max * (int64_t)width * bytes_per_pixel(out_kind) || part_bytes % 16 != 0)
-    return err(RTX_E_ARG, "part_bytes must hold the longest share's tile and be a multiple of 16%s (%lld)", "", part_bytes);
+  if (part_bytes < rows_max * (int64_t)width * out_bytes_per_pixel(out_kind) || part_bytes % 16 != 0)
+    return rtx_fail(RTX_E_ARG, "part_bytes must hold the longest share's tile and be a multiple of 16 (%lld)",
+                    (long long)part_bytes);
   for (int s = 0; s < slots; ++s) {
     if (rank == root && (world > 1 || loop) && (!recv || !recv[s]))
-      return err(RTX_E_ARG, "the root needs a receive buffer per slot%s", "");
+      return rtx_fail(RTX_E_ARG, "the root needs a receive buffer per slot");
     if ((rank != root || loop) && (!send || !send[s]))
-      return err(RTX_E_ARG, "a peer (or a loopback plan) needs a send buffer per slot%s", "");
+      return rtx_fail(RTX_E_ARG, "a peer (or a loopback plan) needs a send buffer per slot");
   }
   Tiles* t = new Tiles{};
   t->comm = (ncclComm_t)comm;
@@ -271,7 +253,7 @@ int rtx_tiles_create(void* comm, int world, int rank, int root, int width, int h
   // uniform runs (root_run == run) keep rank order whatever the root; otherwise the root is rank 0
   t->first = rank == 0 ? 0 : root_run + (rank - 1) * run;
   t->my_run = rank == 0 ? root_run : run;
-  t->local_rows = local_rows(height, row_block, np, t->first, t->my_run);
+  t->local_rows = tile_local_rows(height, row_block, np, t->first, t->my_run);
   t->loop = loop;
   t->rows = rows;
   t->timed = (flags & RTX_TILES_TIMED) && (world > 1 || loop);
@@ -291,7 +273,7 @@ int rtx_tiles_create(void* comm, int world, int rank, int root, int width, int h
   }
   if (e != hipSuccess) {
     rtx_tiles_destroy(t);
-    return err(RTX_E_LAUNCH, "rtx_tiles_create: %s", hipGetErrorString(e));
+    return rtx_fail(RTX_E_LAUNCH, "rtx_tiles_create: %s", hipGetErrorString(e));
   }
   *plan_out = t;
   return RTX_OK;
@@ -301,18 +283,18 @@ int rtx_tiles_submit(void* plan, int slot, const double* scene, int n_spheres, i
                      size_t workspace_bytes, unsigned flags, uint32_t* deferred_out, const uint32_t* tile_order,
                      uint32_t* tile_cost, void* frame, void* stream) {
   Tiles* t = (Tiles*)plan;
-  if (!t) return err(RTX_E_ARG, "null plan%s", "");
-  if (slot < 0 || slot >= t->slots) return err(RTX_E_ARG, "bad slot%s (%lld)", "", slot);
+  if (!t) return rtx_fail(RTX_E_ARG, "null plan");
+  if (slot < 0 || slot >= t->slots) return rtx_fail(RTX_E_ARG, "bad slot (%d)", slot);
   hipStream_t s = (hipStream_t)stream;
   const bool root = t->rank == t->root;
-  if (root && !frame) return err(RTX_E_ARG, "the root needs a frame buffer%s", "");
+  if (root && !frame) return rtx_fail(RTX_E_ARG, "the root needs a frame buffer");
   // a one-rank plan without loopback renders straight into the caller's frame on the caller's
   // stream: stream order is all the ordering it needs (no event: each costs the stream a barrier)
   const bool single = t->world == 1 && !t->loop;
   // the slot's buffers are free once its previous frame's gather and assembly have run
   if (t->used[slot] && !single) {
     if (hipError_t e = hipStreamWaitEvent(s, t->done[slot], 0))
-      return err(RTX_E_LAUNCH, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+      return rtx_fail(RTX_E_LAUNCH, "hipStreamWaitEvent: %s", hipGetErrorString(e));
   }
   t->used[slot] = true;
   // a single part IS the frame (local rows = global rows): render straight into it
@@ -328,7 +310,7 @@ int rtx_tiles_submit(void* plan, int slot, const double* scene, int n_spheres, i
   hipError_t e = hipEventRecord(t->rendered[slot], s);
   if (e == hipSuccess) e = hipStreamWaitEvent(t->cs, t->rendered[slot], 0);
   if (e == hipSuccess && t->timed) e = hipEventRecord(t->g0[slot], t->cs);
-  if (e != hipSuccess) return err(RTX_E_LAUNCH, "event: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return rtx_fail(RTX_E_LAUNCH, "event: %s", hipGetErrorString(e));
   if (t->rows) return gather_rows(t, slot, root, (uint8_t*)frame);
   if (ncclResult_t r = g_rccl.group_start()) return nccl_err("ncclGroupStart", r);
   ncclResult_t r = ncclSuccess;
@@ -348,38 +330,38 @@ int rtx_tiles_submit(void* plan, int slot, const double* scene, int n_spheres, i
   if (r != ncclSuccess) return nccl_err(root ? "ncclRecv" : "ncclSend", r);
   if (r2 != ncclSuccess) return nccl_err("ncclGroupEnd", r2);
   if (t->timed && (e = hipEventRecord(t->g1[slot], t->cs)))
-    return err(RTX_E_LAUNCH, "hipEventRecord: %s", hipGetErrorString(e));
+    return rtx_fail(RTX_E_LAUNCH, "hipEventRecord: %s", hipGetErrorString(e));
   if (root) {
     if (int rc = rtx_assemble_runs(t->recv[slot], t->part_bytes, t->world, t->root_run, t->run, t->width, t->height,
                                    t->row_block, t->out_kind, frame, t->cs))
       return rc;
   }
   if (t->timed && (e = hipEventRecord(t->a1[slot], t->cs)))
-    return err(RTX_E_LAUNCH, "hipEventRecord: %s", hipGetErrorString(e));
-  if ((e = hipEventRecord(t->done[slot], t->cs))) return err(RTX_E_LAUNCH, "hipEventRecord: %s", hipGetErrorString(e));
+    return rtx_fail(RTX_E_LAUNCH, "hipEventRecord: %s", hipGetErrorString(e));
+  if ((e = hipEventRecord(t->done[slot], t->cs))) return rtx_fail(RTX_E_LAUNCH, "hipEventRecord: %s", hipGetErrorString(e));
   return RTX_OK;
 }
 
 int rtx_tiles_timing(void* plan, int slot, float* gather_ms, float* assemble_ms) {
   Tiles* t = (Tiles*)plan;
-  if (!t || !gather_ms || !assemble_ms) return err(RTX_E_ARG, "null argument%s", "");
-  if (slot < 0 || slot >= t->slots) return err(RTX_E_ARG, "bad slot%s (%lld)", "", slot);
-  if (!t->timed) return err(RTX_E_ARG, "the plan was not created with RTX_TILES_TIMED (or does not gather)%s", "");
-  if (!t->used[slot]) return err(RTX_E_ARG, "slot%s %lld has carried no frame", "", slot);
+  if (!t || !gather_ms || !assemble_ms) return rtx_fail(RTX_E_ARG, "null argument");
+  if (slot < 0 || slot >= t->slots) return rtx_fail(RTX_E_ARG, "bad slot (%d)", slot);
+  if (!t->timed) return rtx_fail(RTX_E_ARG, "the plan was not created with RTX_TILES_TIMED (or does not gather)");
+  if (!t->used[slot]) return rtx_fail(RTX_E_ARG, "slot %d has carried no frame", slot);
   hipError_t e = hipEventSynchronize(t->a1[slot]);
   if (e == hipSuccess) e = hipEventElapsedTime(gather_ms, t->g0[slot], t->g1[slot]);
   if (e == hipSuccess) e = hipEventElapsedTime(assemble_ms, t->g1[slot], t->a1[slot]);
-  if (e != hipSuccess) return err(RTX_E_LAUNCH, "rtx_tiles_timing: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return rtx_fail(RTX_E_LAUNCH, "rtx_tiles_timing: %s", hipGetErrorString(e));
   return RTX_OK;
 }
 
 int rtx_tiles_finish(void* plan, int slot, void* stream) {
   Tiles* t = (Tiles*)plan;
-  if (!t) return err(RTX_E_ARG, "null plan%s", "");
-  if (slot < 0 || slot >= t->slots) return err(RTX_E_ARG, "bad slot%s (%lld)", "", slot);
+  if (!t) return rtx_fail(RTX_E_ARG, "null plan");
+  if (slot < 0 || slot >= t->slots) return rtx_fail(RTX_E_ARG, "bad slot (%d)", slot);
   if (!t->used[slot] || (t->world == 1 && !t->loop)) return RTX_OK;  // direct: in stream order already
   if (hipError_t e = hipStreamWaitEvent((hipStream_t)stream, t->done[slot], 0))
-    return err(RTX_E_LAUNCH, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+    return rtx_fail(RTX_E_LAUNCH, "hipStreamWaitEvent: %s", hipGetErrorString(e));
   return RTX_OK;
 }
 

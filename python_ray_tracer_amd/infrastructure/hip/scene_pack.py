@@ -292,7 +292,7 @@ def _apply_camera(blob: np.ndarray, cpos, W: int, H: int) -> None:
 # C passes within R of (Cx, Cz) (projection shortens distances), so its plane point's x lies where
 # the half-lines from (Ox, Oz) through (x, 0) meet the disc (Cx, Cz; R): between the two tangents'
 # crossings of z = 0, both tangent directions heading towards the plane (else unbounded); likewise
-# y on the yz plane. R is r plus the doubled culling margin (rtx_kernels.hip wave_frustum), which
+# y on the yz plane. R is r plus the doubled culling margin (rtx_device.h wave_frustum), which
 # covers the reference root's rounding and the ray direction's normalisation; the box is padded for this function's own rounding and for
 # the lane's plane point Ox + fl(x - Ox), within an ulp of x.
 # the culled kernels (from BVH_MIN_SPHERES): the small-scene kernels gain nothing from them (A/B r5t,
@@ -343,7 +343,7 @@ def sphere_plane_boxes(geo: np.ndarray, cpos) -> np.ndarray:
 def is_tame(geo: np.ndarray, cpos) -> bool:
     """RTX_H_TAME: every sphere centre coordinate, radius and camera coordinate below 2^60 in
     magnitude (finite). Origins of every later ray then stay below ~2^140 (hits lie closer than
-    FARAWAY), which the kernel's half-b sphere test relies on (rtx_kernels.hip, SphTest)."""
+    FARAWAY), which the kernel's half-b sphere test relies on (rtx_device.h, SphTest)."""
     vals = np.concatenate([geo[:, L.G_CX:L.G_CZ + 1].ravel(), 1.0 / geo[:, L.G_INVR],
                            np.asarray(cpos, dtype=np.float64)])
     return bool(np.all(np.abs(vals) < L.TAME_BOUND))
@@ -353,7 +353,7 @@ def is_tame(geo: np.ndarray, cpos) -> bool:
 # Scenes with many spheres get a tree of axis-aligned boxes over the small spheres (surface-area
 # split, up to BVH_LEAF spheres per leaf: 8 measured best, 6-8 within 0.5%); huge spheres (the R=99999 ground) are tested by every
 # ray. The kernel's node test is conservative (margins far above the reference formula's rounding
-# error, rtx_kernels.hip node_may_hit), so culling changes no result bit. The tree only reorders
+# error, rtx_device.h node_may_hit), so culling changes no result bit. The tree only reorders
 # which spheres a ray examines.
 BVH_MIN_SPHERES = 8
 BVH_LEAF = 8

@@ -6,7 +6,7 @@ row_block consecutive rows of every cycle. Interleaving
 balances the load: sky rows (no hit, ~15 flops/pixel) and ground rows (thousands) alternate
 across ranks instead of landing on one rank as contiguous strips would. Local row ``lr`` of part
 ``p`` is global row ``((lr // rb) * P + p) * rb + lr % rb`` — the mapping the kernel uses
-(``global_row`` in rtx_kernels.hip).
+(``global_row`` in rtx_device.h).
 
 Gather layout: every part travels as one flat buffer of ``part_len`` elements (the same length on
 every rank, as a collective needs), holding that part's tile exactly as ``render_tile`` returns

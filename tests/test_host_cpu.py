@@ -34,9 +34,10 @@ def test_library_exports_every_header_symbol():
 
 
 def test_library_links_both_units():
-    """librtx_hip.so is two translation units (csrc/rtx_kernels.hip + csrc/rtx_small.hip, the
-    small-scene kernels): the launch entry of the small unit is defined inside the library (a
-    one-unit build would leave it undefined, found only at the first small-scene render) and hidden."""
+    """librtx_hip.so is several translation units (csrc/rtx_kernels.hip, csrc/rtx_small.hip with the
+    small-scene kernels, ...): the launch entry of the small unit is defined inside the library (a
+    build without that unit would leave it undefined, found only at the first small-scene render) and
+    hidden."""
     L.load()
     so = str(REPO / "python_ray_tracer_amd" / "librtx_hip.so")
     import shutil
@@ -50,6 +51,47 @@ def test_library_links_both_units():
     assert re.search(r"^\w+ t rtx_launch_small\(", local, re.M), "rtx_launch_small: not a hidden definition"
     dynamic = subprocess.run([nm, "-D", so], check=True, capture_output=True, text=True).stdout
     assert "rtx_launch_small" not in dynamic
+
+
+def test_every_kernel_has_one_home(tmp_path):
+    """Each kernel is compiled in one translation unit only: the library embeds one code object per
+    device unit (every csrc/*.hip that includes the device header), and no kernel symbol occurs in
+    two of them. The kernels below are launched from rtx_kernels.hip alone; a unit that compiled
+    their text as well would carry a dead copy."""
+    import shutil
+
+    from pathlib import Path
+
+    from python_ray_tracer_amd import _build
+
+    L.load()
+    try:  # ROCm's own LLVM tools, when PATH lacks them
+        rocm = Path(_build.hipcc()).resolve().parent.parent
+        beside = os.pathsep.join(str(rocm / d) for d in ("lib/llvm/bin", "llvm/bin"))
+    except FileNotFoundError:
+        beside = ""
+    tools = [shutil.which(t) or shutil.which(t, path=beside) for t in ("llvm-objdump", "llvm-readelf")]
+    if None in tools:
+        pytest.skip("no llvm-objdump / llvm-readelf")
+    objdump, readelf = tools
+    so = tmp_path / "librtx_hip.so"
+    shutil.copyfile(REPO / "python_ray_tracer_amd" / "librtx_hip.so", so)
+    subprocess.run([objdump, "--offloading", so.name], check=True, capture_output=True, cwd=tmp_path)
+    objects = sorted(tmp_path.glob(so.name + ".*gfx950*"))
+    csrc = REPO / "python_ray_tracer_amd" / "csrc"
+    device_units = [u for u in csrc.glob("*.hip") if "rtx_device.h" in u.read_text()]
+    assert len(device_units) >= 4 and len(objects) == len(device_units), (objects, device_units)
+    homes = {}  # kernel symbol -> the code objects that define it (the dynamic and the full symbol table list it)
+    for obj in objects:
+        table = subprocess.run([readelf, "-s", "--wide", str(obj)], check=True, capture_output=True, text=True).stdout
+        for row in table.splitlines():
+            f = row.split()
+            if len(f) == 8 and f[3] == "FUNC" and f[6] != "UND":
+                homes.setdefault(f[7], set()).add(obj.name)
+    assert len(homes) > 100, len(homes)
+    assert {k: v for k, v in homes.items() if len(v) > 1} == {}
+    for kernel in ("k_render_general", "k_ray_dirs", "k_intersect", "k_selftest_math", "k_assemble_rows"):
+        assert sum(len(v) for k, v in homes.items() if kernel in k) == 1, (kernel, homes)
 
 
 def test_abi_layout_matches_header():
@@ -602,7 +644,7 @@ def test_shadow_grid_masks_are_conservative(n_spheres, light):
     """scene_pack's shadow grid (RTX_H_SHGRID): for hit points sampled on every sphere's surface and
     on the ground (inside and far outside the grid), any sphere the reference's shadow test
     (shader.py:126-128: oracle.intersect from the nudged point along L_dir) reports as hit must be in
-    the mask the kernel would pick (rtx_kernels.hip grid_mask): the voxel's when the nudged point lies
+    the mask the kernel would pick (rtx_device.h grid_mask): the voxel's when the nudged point lies
     in the grid, else the huge spheres' when the ray's line misses the small spheres' ball."""
     spec = scenes.random_spec(n_spheres, 7, 64, 36)
     if light is not None:
@@ -660,7 +702,7 @@ def test_shadow_grid_masks_are_conservative(n_spheres, light):
 
 
 def _beam_candidates(G, Oc, A, r2, omc, drop_rho=False):
-    """Numpy restatement of rtx_kernels.hip wave_beam for one wave: G = [S, 4] (centre, radius),
+    """Numpy restatement of rtx_device.h wave_beam for one wave: G = [S, 4] (centre, radius),
     Oc / A the first active lane's origin / direction, r2 / omc the active lanes' |O - Oc|^2 and
     1 - D.A. Returns the candidate flags, or None where the kernel falls back to the culling tree."""
     def p2above(x, lo, hi):
@@ -691,7 +733,7 @@ def _beam_candidates(G, Oc, A, r2, omc, drop_rho=False):
 
 @pytest.mark.parametrize("seed", [0, 3])
 def test_wave_beam_is_conservative(seed):
-    """The reflected-ray beam cull (rtx_kernels.hip wave_beam, levels >= 1 of scenes of 32 spheres and
+    """The reflected-ray beam cull (rtx_device.h wave_beam, levels >= 1 of scenes of 32 spheres and
     more): for every 8x8 wave tile and random subsets of its live lanes (the lanes still bouncing), any
     sphere that the reference's intersect (shape.py:28-51, oracle) reports a hit for on a live lane's
     reflected ray must be a candidate. Mutation check: without the origin ball's radius rho some

@@ -1,4 +1,4 @@
-"""The kernels' sin (rtx_kernels.hip sin_reduced, used for the iridescence phase, shader.py:211)
+"""The kernels' sin (rtx_device.h sin_reduced, used for the iridescence phase, shader.py:211)
 is within 2 ulp of the true sine. NumPy's own SIMD sin is not correctly rounded either (~1 ulp), so
 the render parity bar is the colour tolerance of tests/test_gpu_parity.py, not bit equality.
 
@@ -48,7 +48,7 @@ int main(void) {
 
 
 def _device_function():
-    src = (REPO / "python_ray_tracer_amd" / "csrc" / "rtx_kernels.hip").read_text()
+    src = (REPO / "python_ray_tracer_amd" / "csrc" / "rtx_device.h").read_text()
     m = re.search(r"__device__ __forceinline__ double sin_reduced\(double x\) \{.*?\n\}\n", src, re.S)
     assert m, "sin_reduced not found"
     body = m.group(0).replace("__device__ __forceinline__", "static")

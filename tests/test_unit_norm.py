@@ -1,4 +1,4 @@
-"""The closed form the kernels use to re-normalise an already-unit vector (rtx_kernels.hip,
+"""The closed form the kernels use to re-normalise an already-unit vector (rtx_device.h,
 inv_mag_near1) equals the reference's correctly rounded ``1.0 / sqrt(d)`` chain
 (NumpyVector3D.norm, ray_tracer/infrastructure/numpy/base.py:61-64) for every squared length d
 within 2^-30 of 1: checked exhaustively against IEEE sqrt and division on the host. (The device

@@ -1,14 +1,15 @@
 """Static instruction budget of one kernel in a gfx950 assembly dump, by source function.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -disable-machine-licm \
-          -gline-tables-only --cuda-device-only -S -o rtx.s python_ray_tracer_amd/csrc/rtx_kernels.hip
+          -gline-tables-only --cuda-device-only -S -o rtx.s python_ray_tracer_amd/csrc/rtx_kernels.hip   (or another unit)
     python tools/isa_budget.py rtx.s '_ZN12_GLOBAL__N_113k_render_fastILi3ELb1ELi0ELb0ELi2ELb0ELi0ELi0EEEvNS_6ParamsE'
 
 (the second argument names a kernel: here k_render_fast<B = 3, LDS, DEEP 0, STATS = false, TP 2, IMG =
 false, NSPH 0, WAVES 0>, the persistent capped kernel of cap 3)
 
-Every instruction is attributed to the innermost source line of its `.loc` (inlined helpers keep
-their own lines) and that line to the enclosing function of rtx_kernels.hip; instructions are
+Every instruction is attributed to the innermost (file, line) of its `.loc` (inlined helpers keep
+their own lines) and that line to the enclosing function of its file, the device header
+csrc/rtx_device.h or the compiled unit; instructions are
 classified (f64 arithmetic, f64 transcendental, compares, 64-bit selects, moves, other VALU, SALU,
 scalar/vector/LDS memory, scratch, waitcnt, branches). Static counts: a loop body counts once. The
 register/spill metadata of the kernel is printed too.
@@ -21,7 +22,8 @@ import sys
 from collections import Counter, defaultdict
 from pathlib import Path
 
-SRC = Path(__file__).resolve().parent.parent / "python_ray_tracer_amd" / "csrc" / "rtx_kernels.hip"
+CSRC = Path(__file__).resolve().parent.parent / "python_ray_tracer_amd" / "csrc"
+SRC = CSRC / "rtx_device.h"  # k_render_fast and what it inlines: the file of the stage lines
 
 CLASSES = ("f64", "f64_trans", "cmp", "cndmask", "mov", "valu_other", "salu", "smem", "lds", "vmem", "scratch",
            "waitcnt", "branch", "other")
@@ -81,8 +83,8 @@ def source_functions(path: Path):
 
 
 def _chain(comment: str):
-    """Source lines of a .loc comment's inline chain, innermost first (file rtx_kernels.hip)."""
-    return [int(m) for m in re.findall(r"rtx_kernels\.hip:(\d+):\d+", comment)]
+    """Source lines of a .loc comment's inline chain, innermost first (file rtx_device.h)."""
+    return [int(m) for m in re.findall(re.escape(SRC.name) + r":(\d+):\d+", comment)]
 
 
 def stages(asm_path: str, symbol: str, root_line: int, outer: tuple, inner: tuple | None = None):
@@ -120,25 +122,24 @@ def stages(asm_path: str, symbol: str, root_line: int, outer: tuple, inner: tupl
 
 
 def main(asm_path: str, symbol: str) -> None:
-    funcs = source_functions(SRC)
+    by_func = defaultdict(Counter)
+    by_line = defaultdict(Counter)
+    meta = {}
+    # the .file indices of the library's own sources (the device header and the compiled unit)
+    files = {}
+    with open(asm_path) as f:
+        for raw in f:
+            m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', raw)
+            if m and (CSRC / Path(m.group(3) or m.group(2)).name).exists():
+                files[m.group(1)] = CSRC / Path(m.group(3) or m.group(2)).name
+    funcs = {fi: source_functions(path) for fi, path in files.items()}
 
-    def func_of(line: int) -> str:
-        for a, b, n in funcs:
+    def func_of(fi: str, line: int) -> str:
+        for a, b, n in funcs[fi]:
             if a <= line <= b:
                 return n
         return f"line{line}"
 
-    by_func = defaultdict(Counter)
-    by_line = defaultdict(Counter)
-    meta = {}
-    # the .file index of rtx_kernels.hip (0 when it is the compiled unit; rtx_small.hip includes it)
-    kfile = "0"
-    with open(asm_path) as f:
-        for raw in f:
-            m = re.match(r'\s*\.file\s+(\d+)\s+"[^"]*"(?:\s+"([^"]*)")?', raw)
-            if m and (m.group(2) or "").endswith(SRC.name) or (m and m.group(2) is None and SRC.name in raw):
-                kfile = m.group(1)
-                break
     inside = False
     cur = ("?", 0)
     with open(asm_path) as f:
@@ -158,7 +159,7 @@ def main(asm_path: str, symbol: str) -> None:
                 continue
             op = s.split()[0]
             c = classify(op)
-            key = func_of(cur[1]) if cur[0] == kfile else f"hdr{cur[0]}"
+            key = func_of(*cur) if cur[0] in files else f"hdr{cur[0]}"
             by_func[key][c] += 1
             by_line[cur][c] += 1
     # kernel resource metadata (the .amdhsa block after the function)
@@ -187,9 +188,10 @@ def main(asm_path: str, symbol: str) -> None:
     for name, c in sorted(by_func.items(), key=lambda kv: -sum(kv[1].values())):
         print(f"{name:28s}" + "".join(f"{c[k]:10d}" for k in CLASSES) + f"{sum(c.values()):8d}")
     print(f"{'TOTAL':28s}" + "".join(f"{total[k]:10d}" for k in CLASSES) + f"{sum(total.values()):8d}")
-    print(f"\ntop source lines (file {kfile} = rtx_kernels.hip):")
+    print("\ntop source lines (" + ", ".join(f"file {fi} = {p.name}" for fi, p in sorted(files.items())) + "):")
+    text_of = {fi: p.read_text().splitlines() for fi, p in files.items()}
     for (fi, ln), c in sorted(by_line.items(), key=lambda kv: -sum(kv[1].values()))[:40]:
-        src = SRC.read_text().splitlines()[ln - 1].strip()[:70] if fi == kfile and ln > 0 else ""
+        src = text_of[fi][ln - 1].strip()[:70] if fi in files and ln > 0 else ""
         print(f"  {fi}:{ln:5d} {sum(c.values()):5d}  {dict(c.most_common(4))}  {src}")
 
 

@@ -1,14 +1,15 @@
 """Registers, spills and scratch of every k_render_fast instantiation, from hipcc's
 -Rpass-analysis=kernel-resource-usage remarks (no GPU needed).
 
-    python tools/resource_usage.py [SOURCE.hip ...]      (default: csrc/rtx_kernels.hip)
+    python tools/resource_usage.py [SOURCE.hip ...]      (default: every unit of csrc/ that has such kernels)
 
 Compiles each source for gfx950 with the library's flags (device only, in parallel) and prints one
 row per instantiation: template arguments <B, LDS, DEEP, STATS, TP, IMG, NSPH[, WAVES]>, VGPRs, VGPR
 spills, scratch bytes per lane, occupancy, SGPRs and LDS bytes, side by side for the sources given
-(A/B variants of the kernel file must sit next to it, e.g. csrc/_ab_x.hip, so that its relative
-#include resolves). Revisions up to 896f684 carried one more argument after DEEP (a flag of the
-retired backward fold, false in every kernel they could launch); it is dropped from the row key, so
+(the units of an A/B variant sit in a sibling directory of csrc/, python_ray_tracer_amd/_ab_<name>/,
+as tools/ab_build.py lays them out, so that their relative #include resolves). Revisions up to
+896f684 carried one more argument after DEEP (a flag of the retired backward fold, false in every
+kernel they could launch); it is dropped from the row key, so
 that such a revision (tools/ab_build.py --rev) and the present file share rows, and shown as a
 trailing "+" where it was true.
 """
@@ -54,14 +55,15 @@ def usage(text: str) -> dict:
 
 
 def main():
-    # default: the library's two units (the small-scene kernels live in rtx_small.hip, built with
-    # _build.SMALL_FLAGS); each source is a column
-    srcs = [Path(s) for s in sys.argv[1:]] or [_build.SRC, _build.SMALL_SRC]
-    procs = [subprocess.Popen([_build.hipcc(), *FLAGS, *(_build.SMALL_FLAGS if "small" in s.name else []),
-                               "--cuda-device-only", "-c",
+    # default: the library's device units; each unit's own flags by its stem (_build.UNIT_FLAGS)
+    given = [Path(s) for s in sys.argv[1:]]
+    srcs = given or [s for s, _ in _build.library_units() if _build.DEVICE_HDR.name in s.read_text()]
+    procs = [subprocess.Popen([_build.hipcc(), *FLAGS, *_build.UNIT_FLAGS.get(s.stem, []), "--cuda-device-only", "-c",
                                "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null", str(s)],
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for s in srcs]
     res = [{demangle_args(n): u for n, u in usage(p.communicate()[0]).items()} for p in procs]
+    if not given:  # a column per unit that instantiates k_render_fast
+        srcs, res = zip(*[(s, r) for s, r in zip(srcs, res) if r])
     print("instantiation".ljust(18) + "".join(f"| {s.stem[:16]:16s} vgpr spill scr occ sgpr   lds " for s in srcs))
     for n in sorted(set().union(*res)):
         row = n.ljust(18)
