@@ -25,6 +25,8 @@
  *                          nearest distance and hit shape of raytrace_scene (base.py:97-103), P, the
  *                          normal and is_in_light of NumpyShader.create (shader.py:73-84) and
  *                          Texture.get_color — which the reference computes and discards
+ *   rtx_camera_rays     <- generalises get_ray_directions (base.py:123-141): the rays of a camera with
+ *                          a target, an up vector, a field of view and a thin lens (PerspectiveCamera)
  *   rtx_edge_mask, rtx_sample_dirs, rtx_resolve_scatter
  *                       <- no counterpart: adaptive anti-aliasing (HipRenderer(samples=k,
  *                          adaptive=True)): which pixels of a plain frame are edges, the k x k sample
@@ -60,7 +62,7 @@ extern "C" {
 
 #define RTX_ABI_VERSION 3 /* 2: rtx_resolve_samples; 3: rtx_last_launches, RTX_WS_COUNTER_BYTES */
 /* (rtx_primary_aovs*, rtx_edge_mask, rtx_sample_dirs and rtx_resolve_scatter were added to version 3:
- * new symbols only, nothing that existed changed) */
+ * new symbols only, nothing that existed changed; so was rtx_camera_rays) */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -472,6 +474,48 @@ int rtx_sample_dirs(const double* sample_scene, int k, int width, int height, co
                     int n_flagged, double* dirs_out, void* stream);
 int rtx_resolve_scatter(const double* samples_f64, int k, const int32_t* pixels_i32, int n_flagged,
                         int width, int height, void* out, int out_kind, void* stream);
+
+/* A perspective camera's ray generator (HipRenderer with a domain.PerspectiveCamera).
+ * It generalises get_ray_directions (base.py:123-141: one shared origin in front of a screen fixed at
+ * z = 0, looking along +z) to a camera with a position, a target, an up vector, a vertical field of
+ * view and a thin lens. The host (python_ray_tracer_amd/camera.py) reduces the camera to six vectors,
+ * the camera record: RTX_CAM_WORDS doubles, vector v at cam[RTX_C_v .. RTX_C_v + 2], the rest zero.
+ *   EYE  E  = position
+ *   FWD  C  = fwd * F            the centre of the plane in focus (F: the focus distance)
+ *   U    U  = right * (hw * F)   half its width   (hw = tan(fov / 2) * width / height)
+ *   V    V  = tup * (hh * F)     half its height  (hh = tan(fov / 2))
+ *   LU   LU = right * lens_radius,  LV = tup * lens_radius   (all zero: a pinhole)
+ * The rays of one row tile (the tile geometry and local row order of rtx_render_camera_sched), k x k
+ * samples per pixel, n = k*k*width*n_local_rows of them in the order of a sample frame's rows: the ray
+ * of local row lr, column c, sample (sy, sx) has index (k*lr + sy) * (k*width) + k*c + sx, which is
+ * the layout rtx_resolve_samples reads. With gr the global row of lr, ix = k*c + sx, iy = k*gr + sy,
+ * in float64 without contraction and in exactly this order:
+ *   iw = 1.0 / (double)(k*width);  ih = 1.0 / (double)(k*height)
+ *   u = (double)(2*ix + 1) * iw - 1.0;  v = 1.0 - (double)(2*iy + 1) * ih
+ *   h = (uint32)c * 0x9E3779B1u ^ (uint32)gr * 0x85EBCA77u
+ *   h ^= h >> 16;  h *= 0x7FEB352Du;  h ^= h >> 15;  h *= 0x846CA68Bu;  h ^= h >> 16
+ *   j = ((sy*k + sx) + h % (k*k)) % (k*k)        a per-pixel rotation of the lens table
+ *   (a, b) = lens ? (lens[j], lens[k*k + j]) : (0, 0)
+ *   off = LU * a + LV * b                        per component: LU.x * a + LV.x * b
+ *   origin = E + off
+ *   d = ((C + U * u) + V * v) - off              aims at the point of the focus plane behind (u, v)
+ *   dir = d * (1.0 / sqrt((d.x*d.x + d.y*d.y) + d.z*d.z))        the reference's norm(), base.py:61-64
+ * cam is a HOST pointer, read during the call (the record travels as a kernel argument). lens:
+ * device double [2][k*k], the k*k points of the unit disk the samples of a pixel leave through (x
+ * plane, then y plane); NULL takes (0, 0) for every sample. origins_out: device double [3][n], or
+ * NULL to store no origins; dirs_out: device double [3][n]. A record with a lens (a non-zero word of
+ * LU or LV) needs both lens and origins_out; a pinhole's rays share the origin cam[RTX_C_EYE ..].
+ * Asynchronous on `stream`, never allocates, never synchronises. RTX_E_ARG (before any HIP call) for
+ * a null cam or dirs_out, a non-finite record word, k outside 1..8, bad tile geometry, k*width or
+ * k*height at 2^31 or above, n at 2^31 or above, or a missing lens or origins_out when the record has
+ * a lens; zero rays return RTX_OK without a launch. */
+enum {
+  RTX_CAM_WORDS = 24,
+  RTX_C_EYE = 0, RTX_C_FWD = 3, RTX_C_U = 6, RTX_C_V = 9, RTX_C_LU = 12, RTX_C_LV = 15
+};
+int rtx_camera_rays(const double* cam, const double* lens, int k, int width, int height,
+                    int row_block, int n_parts, int part, int part_run, int n_local_rows,
+                    double* origins_out, double* dirs_out, void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

@@ -21,6 +21,8 @@
 //                     <- no counterpart: adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True);
 //                        rtx_edge_mask, rtx_sample_dirs, rtx_resolve_scatter), with the tensor-size checks
 //                        the bare-pointer C ABI cannot make
+//   rt::camera_rays   <- generalises get_ray_directions (base.py:123-141): the sample rays of a perspective
+//                        camera (domain.PerspectiveCamera; rtx_camera_rays) for a row tile of its frame
 //   rt::status        <- reads and clears the workspace's sticky RTX_ST_* flags
 //   rt::comm_unique_id, rt::comm_init, rt::comm_destroy, rt::tiles_create, rt::tiles_submit,
 //   rt::tiles_finish, rt::tiles_destroy
@@ -54,6 +56,8 @@
 #include <torch/library.h>
 
 #include <mutex>
+#include <optional>
+#include <tuple>
 #include <vector>
 
 #include "../../include/rtx_hip.h"
@@ -580,6 +584,56 @@ void resolve_scatter(const at::Tensor& samples, int64_t k, const at::Tensor& pix
            "rtx_resolve_scatter");
 }
 
+// ---- a perspective camera's rays (rtx_camera_rays) -----------------------------------------------
+// cam: the camera record, a HOST float64 tensor of RTX_CAM_WORDS words (it travels as a kernel
+// argument); lens: the device lens table [2, k*k] or None. Returns (origins or None, dirs): origins
+// [3, n] when a lens table is given, else None (a pinhole's rays share the origin cam[RTX_C_EYE ..]).
+// The sizes of both tensors are checked here: the C ABI takes bare pointers. Returns the rays of a
+// plane, n. Shared by the kernel and its Meta form.
+int64_t check_camera_rays(const at::Tensor& cam, const std::optional<at::Tensor>& lens, int64_t k, int64_t width,
+                          int64_t height, int64_t row_block, int64_t n_parts, int64_t part, int64_t part_run) {
+  TORCH_CHECK(cam.scalar_type() == at::kDouble && cam.dim() == 1 && cam.numel() == RTX_CAM_WORDS,
+              "cam must be the camera record: ", at::kDouble, " [", (int)RTX_CAM_WORDS, "], got ", cam.scalar_type(), " ",
+              cam.sizes());
+  TORCH_CHECK(k >= 1 && k <= 8, "k (samples per pixel side) must be in 1..8, got ", k);
+  check_tile(width, height, row_block, n_parts, part, part_run);
+  TORCH_CHECK(k * width < 2147483648LL && k * height < 2147483648LL, "k*width and k*height must stay below 2^31");
+  const int64_t rows = tile_rows(height, row_block, n_parts, part, part_run);
+  TORCH_CHECK((double)(k * k) * (double)width * (double)rows < 2147483648.0,
+              "k*k*width*rows must stay below 2^31 rays");
+  if (lens.has_value()) {
+    TORCH_CHECK(lens->scalar_type() == at::kDouble && lens->numel() == 2 * k * k, "lens must be ", at::kDouble,
+                " [2, k*k] = ", 2 * k * k, " words, got ", lens->scalar_type(), " with ", lens->numel());
+  }
+  return k * k * width * rows;
+}
+
+std::tuple<std::optional<at::Tensor>, at::Tensor> camera_rays(const at::Tensor& cam,
+                                                             const std::optional<at::Tensor>& lens, int64_t k,
+                                                             int64_t width, int64_t height, int64_t row_block,
+                                                             int64_t n_parts, int64_t part, int64_t part_run) {
+  TORCH_CHECK(cam.device().is_cpu(), "cam must be a host tensor (the record is a kernel argument), got one on ",
+              cam.device());
+  TORCH_CHECK(cam.is_contiguous(), "cam must be contiguous");
+  if (lens.has_value()) check_gpu(*lens, "lens", at::kDouble);
+  const int64_t n = check_camera_rays(cam, lens, k, width, height, row_block, n_parts, part, part_run);
+  const int64_t rows = tile_rows(height, row_block, n_parts, part, part_run);
+  // without a lens table no argument names a device: the rays land on the current one
+  const at::Device dev = lens.has_value() ? lens->device() : at::Device(at::kCUDA, c10::hip::current_device());
+  const at::OptionalDeviceGuard guard(dev);
+  const auto opts = at::TensorOptions().dtype(at::kDouble).device(dev);
+  std::optional<at::Tensor> origins;
+  if (lens.has_value()) origins = at::empty({3, n}, opts);
+  at::Tensor dirs = at::empty({3, n}, opts);
+  if (n == 0) return {origins, dirs};  // (an empty tensor's pointer may be null)
+  check_rc(rtx_camera_rays(cam.data_ptr<double>(), lens.has_value() ? lens->data_ptr<double>() : nullptr, (int)k,
+                           (int)width, (int)height, (int)row_block, (int)n_parts, (int)part, (int)part_run, (int)rows,
+                           origins.has_value() ? origins->data_ptr<double>() : nullptr, dirs.data_ptr<double>(),
+                           c10::hip::getCurrentHIPStream(dev.index()).stream()),
+           "rtx_camera_rays");
+  return {origins, dirs};
+}
+
 int64_t status(at::Tensor& workspace) {
   check_gpu(workspace, "workspace", at::kByte);
   TORCH_CHECK(workspace.numel() >= RTX_WS_HDR_BYTES, "workspace shorter than its header");
@@ -772,9 +826,23 @@ void resolve_scatter_meta(const at::Tensor& samples, int64_t k, const at::Tensor
   check_scatter(samples, k, pixels, width, height, out, out_kind);
 }
 
+// (on the device of the lens table; without one, of cam: no argument names the GPU the rays land on)
+std::tuple<std::optional<at::Tensor>, at::Tensor> camera_rays_meta(const at::Tensor& cam,
+                                                                  const std::optional<at::Tensor>& lens, int64_t k,
+                                                                  int64_t width, int64_t height, int64_t row_block,
+                                                                  int64_t n_parts, int64_t part, int64_t part_run) {
+  const int64_t n = check_camera_rays(cam, lens, k, width, height, row_block, n_parts, part, part_run);
+  const auto opts = (lens.has_value() ? lens->options() : cam.options()).dtype(at::kDouble);
+  std::optional<at::Tensor> origins;
+  if (lens.has_value()) origins = at::empty({3, n}, opts);
+  return {origins, at::empty({3, n}, opts)};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rt, m) {
+  m.def("camera_rays(Tensor cam, Tensor? lens, int k, int width, int height, int row_block=1, int n_parts=1, "
+        "int part=0, int part_run=1) -> (Tensor?, Tensor)");
   m.def("render_tile(Tensor scene, int n_spheres, int width, int height, int row_block, int n_parts, int part, "
         "int max_bounces, int out_kind, Tensor(a!) workspace, Tensor(b!)? stats=None, bool check=True, "
         "int part_run=1) -> Tensor");
@@ -828,6 +896,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
+  m.impl("camera_rays", &camera_rays);
   m.impl("status", &status);
 }
 
@@ -847,6 +916,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
+  m.impl("camera_rays", &camera_rays);
   m.impl("status", &status);
 }
 
@@ -864,4 +934,5 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("edge_mask", &edge_mask_meta);
   m.impl("sample_dirs", &sample_dirs_meta);
   m.impl("resolve_scatter", &resolve_scatter_meta);
+  m.impl("camera_rays", &camera_rays_meta);
 }

@@ -311,8 +311,13 @@ def tile_gather_for(renderer, scene, *, group=None, row_block: int = 8, dst: int
     import torch.distributed as dist
 
     W, H = int(scene.camera.width), int(scene.camera.height)
+    # a PerspectiveCamera's tile is generated rays traced by render_tile: the native plan (rtx_tiles_submit)
+    # renders the reference camera, so such scenes take render_tile(into=) and the gather, like supersampling
+    from python_ray_tracer_amd.camera import is_perspective
+
+    native = False if is_perspective(scene.camera) else None
     key = (W, H, int(row_block), int(dst), "u8" if out == "u8" else None, id(group), dist.get_world_size(group),
-           getattr(renderer, "color_dtype", None))
+           getattr(renderer, "color_dtype", None), native)
     cache = getattr(renderer, "_tile_gathers", None)
     if cache is None:
         cache = {}
@@ -324,6 +329,7 @@ def tile_gather_for(renderer, scene, *, group=None, row_block: int = 8, dst: int
     if tg is None:
         while len(cache) >= TILE_GATHER_CACHE:
             cache.pop(next(iter(cache)))  # least recently used (dicts keep insertion order)
-        tg = TileGather(renderer, W, H, group=group, row_block=row_block, dst=dst, out=out, slots=1)
+        tg = TileGather(renderer, W, H, group=group, row_block=row_block, dst=dst, out=out, slots=1,
+                        native=native)
     cache[key] = tg  # most recently used last
     return tg

@@ -48,6 +48,28 @@ class Camera:
 
 
 @dataclass
+class PerspectiveCamera(Camera):
+    """A camera that looks from ``position`` at ``target`` (no counterpart in the reference, whose
+    camera always looks along +z through a screen fixed at z=0). ``position``, ``width`` and
+    ``height`` mean what they mean for ``Camera``, so the scene packer and the shader's view vector
+    (``scene.camera.position``) read them unchanged.
+
+    ``up``: the direction that appears upwards in the frame (a Vector3D or three numbers; it need not
+    be perpendicular to the view, only not parallel to it). ``fov``: the vertical field of view in
+    degrees, 0 < fov < 180. ``lens_radius`` >= 0: the radius of a thin lens (0: a pinhole, everything
+    in focus); with a lens each of a pixel's samples leaves through another point of it, so it needs
+    a renderer with ``samples >= 2``. ``focus_distance``: the distance along the view direction of
+    the plane that stays sharp, > 0; None: the target's distance. Validated and reduced to the
+    kernel's camera record by ``python_ray_tracer_amd.camera``."""
+
+    target: Vector3D
+    up: object = (0.0, 1.0, 0.0)
+    fov: float = 40.0
+    lens_radius: float = 0.0
+    focus_distance: float | None = None
+
+
+@dataclass
 class PointLight:
     """Reference ``domain.py:26-30``. Only ``scene.lights[0]`` is ever used as the point light
     (``shader.py:75``)."""

@@ -109,6 +109,7 @@ EXPORTS = (
     "rtx_edge_mask",
     "rtx_sample_dirs",
     "rtx_resolve_scatter",
+    "rtx_camera_rays",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -176,6 +177,8 @@ _SIGS = {
                              _c_void_p]),
     "rtx_sample_dirs": (_i32, [_c_void_p, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p]),
     "rtx_resolve_scatter": (_i32, [_c_void_p, _i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p]),
+    "rtx_camera_rays": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p,
+                               _c_void_p, _c_void_p]),
 }
 
 _lib = None

@@ -51,6 +51,14 @@ that device's current HIP stream and returns a new tensor):
   sample scene (the same scene with a k*width x k*height camera); and the resolve of float64
   [3, n*k*k] samples written over the listed pixels of ``out`` ([3, width*height] colour or
   [height, width, 3] uint8, mutated in place; nothing is returned). Every tensor's size is checked.
+* ``rt::camera_rays(cam, lens, k, width, height, row_block=1, n_parts=1, part=0, part_run=1)`` — the
+  sample rays of a perspective camera (domain.PerspectiveCamera; rtx_camera_rays, contract in
+  include/rtx_hip.h) for a row tile of its frame: ``cam`` is the camera record, a HOST float64
+  [24] tensor (``camera.camera_record``; it travels as a kernel argument), ``lens`` the device lens
+  table float64 [2, k*k] (``camera.lens_table``) or None. Returns ``(origins, dirs)``, float64
+  [3, k*k*width*rows] each in the order of a sample frame's rows (what ``rt::resolve_samples`` reads);
+  ``origins`` is None without a lens table (the rays share the origin ``cam[0:3]``, and land on the
+  current device). A record with a lens and no table raises. Both tensors' sizes are checked.
 * ``rt::status(workspace)`` — reads and clears the sticky RTX_ST_* flags (1 stack overflow,
   2 deferred-list overflow, 4 bad scene); synchronises.
 * ``rt::workspace_bytes(n_rays, max_bounces)``.
@@ -79,8 +87,8 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "resolve_samples", "primary_aovs", "primary_aovs_rays", "edge_mask", "sample_dirs", "resolve_scatter", "status",
-       "workspace_bytes",
+       "resolve_samples", "primary_aovs", "primary_aovs_rays", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
+       "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
        "comm_unique_id", "comm_init", "comm_destroy", "tiles_create", "tiles_submit", "tiles_finish",
        "tiles_destroy")
