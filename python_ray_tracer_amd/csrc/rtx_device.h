@@ -35,6 +35,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/rtx_hip.h"
 #include "rtx_internal.h"
@@ -100,6 +101,13 @@ constexpr int kCappedMax = RTX_FAST_MAX_BOUNCES;  // caps rendered entirely by k
 //   2 / 4 = also V and H (2) or H (4) by rsq + Newton: N.V near grazing amplifies their rounding,
 //       C4 and 1080p colour moved by 1.4e-12 (over the 1e-12 bar), not adopted.
 constexpr int kShadeMath = 3;
+// The small-scene wave (small_wave, TP 0), each switch an A/B of its own (profiles/optimistic_C2_ab.json):
+// the optimistic first body of the counter-free capped builds, one guard verdict per wave instead of
+// a ballot and a branch per helper; false: the guarded body alone
+constexpr bool kSmallOptimistic = true;
+// the sphere table requested with the header words and held in registers until the level-0 search
+// has found a hit (an all-sky wave never waits for it); false: staged in LDS before the tile
+constexpr bool kSmallLateStage = true;
 // ---- derived ----
 constexpr int kWaveH = 64 / kWaveW;
 static_assert(kFastWaves == 1 || kFastWaves == 2 || kFastWaves == 4, "kFastWaves");
@@ -194,6 +202,9 @@ struct Params {
   const uint32_t* tile_order;
   uint32_t* tile_cost;
   int reserve;  // RTX_F_RESERVE: block slots the persistent launch leaves free (host side only)
+  // small-scene launches (rtx_small.hip sets it): floor(2^32 / grid.x), or 2^32 - 1 for grid.x == 1;
+  // small_wave divides a tile_order entry by grid.x with it
+  uint32_t tile_div;
 };
 
 // Deferred-list entry (uint64): pixel | frame << 40 | (rays counted through level a) + 1 << 56 |
@@ -265,6 +276,23 @@ __device__ __forceinline__ double dot3(double ax, double ay, double az, double b
   return ((ax * bx) + (ay * by)) + (az * bz);  // NumpyVector3D.dot, base.py:34-35
 }
 
+// The range-checked helpers below (sph_test, inv_mag, inv_mag_unit, sin_ref and what calls them) take
+// their guard as the type of their `tame` argument. A double (the half-b threshold, or NaN) is the
+// guarded form: one ballot and one wave-uniform branch per helper, the full expansion if any active
+// lane is out of range. Sticky is the optimistic form (fast_tile's first body in the counter-free
+// capped small-scene kernels, tame camera launches only): every helper takes its exact fast core
+// unconditionally and ORs its own guard's failure into the lane's flag, nothing branches on it, and
+// the wave takes one verdict after the bounce loop. A tripped lane's values are garbage from there
+// on, but only values: every index derived downstream (the hit sphere, the LDS offsets, the texture
+// key) comes from comparisons and loop counters, never from arithmetic on such a value.
+struct Sticky {
+  bool& bad;
+  __device__ __forceinline__ operator double() const { return 0x1.0p-350; }  // the tame threshold
+  __device__ __forceinline__ void trip(bool failed) const { bad = bad || failed; }
+};
+template <typename Tm>
+constexpr bool kSticky = std::is_same<Tm, Sticky>::value;
+
 // Correctly rounded sqrt and division, fast paths. LLVM lowers f64 sqrt / fdiv for gfx9 to a
 // correctly rounded sequence (v_rsq_f64 / v_rcp_f64 + Newton-Raphson FMAs) wrapped in operand
 // scaling (v_ldexp, v_div_scale) and special-value fix-ups (v_cmp_class, v_div_fixup). For operands
@@ -313,15 +341,21 @@ __device__ __forceinline__ double div_cr(double a, double b) {
 // 1.0 / where(mag == 0, 1, mag) with mag = sqrt(d), d = |v|^2 (NumpyVector3D.norm, base.py:61-64).
 // d in [2^-600, 2^600] puts sqrt's operand and the quotient's divisor (mag in [2^-300, 2^300],
 // non-zero) in both cores' exact ranges: one wave-uniform check instead of three.
-__device__ __forceinline__ double inv_mag(double d) {
+template <typename Tm = double>
+__device__ __forceinline__ double inv_mag(double d, Tm tame = Tm()) {
+  if constexpr (kSticky<Tm>) {
+    tame.trip(!(d >= 0x1.0p-600 && d <= 0x1.0p+600));
+    return div_core(1.0, sqrt_core(d));
+  }
   if (__ballot(!(d >= 0x1.0p-600 && d <= 0x1.0p+600)) == 0) return div_core(1.0, sqrt_core(d));
   const double mag = sqrt_cr(d);
   return div_cr(1.0, mag == 0.0 ? 1.0 : mag);
 }
 
-__device__ __forceinline__ void norm3(double& x, double& y, double& z) {
+template <typename Tm = double>
+__device__ __forceinline__ void norm3(double& x, double& y, double& z, Tm tame = Tm()) {
   // NumpyVector3D.norm, base.py:61-64: v * (1.0 / where(mag == 0, 1, mag))
-  const double r = inv_mag(dot3(x, y, z, x, y, z));
+  const double r = inv_mag(dot3(x, y, z, x, y, z), tame);
   x = x * r;
   y = y * r;
   z = z * r;
@@ -338,14 +372,20 @@ __device__ __forceinline__ void norm3(double& x, double& y, double& z) {
 __device__ __forceinline__ double inv_mag_near1(double d) {
   return __builtin_fma(-__builtin_floor((d - 1.0) * 0x1.0p51), 0x1.0p-52, 1.0);
 }
-__device__ __forceinline__ double inv_mag_unit(double d) {
+template <typename Tm = double>
+__device__ __forceinline__ double inv_mag_unit(double d, Tm tame = Tm()) {
+  if constexpr (kSticky<Tm>) {
+    tame.trip(!(fabs(d - 1.0) <= 0x1.0p-30));
+    return inv_mag_near1(d);
+  }
   // wave-uniform: the closed form unless some active lane is out of its range
   if (__ballot(!(fabs(d - 1.0) <= 0x1.0p-30)) == 0) return inv_mag_near1(d);
   return inv_mag(d);
 }
-__device__ __forceinline__ void norm3_unit(double& x, double& y, double& z) {
+template <typename Tm = double>
+__device__ __forceinline__ void norm3_unit(double& x, double& y, double& z, Tm tame = Tm()) {
   // NumpyVector3D.norm (base.py:61-64) of a vector expected to be unit up to rounding
-  const double r = inv_mag_unit(dot3(x, y, z, x, y, z));
+  const double r = inv_mag_unit(dot3(x, y, z, x, y, z), tame);
   x = x * r;
   y = y * r;
   z = z * r;
@@ -421,9 +461,15 @@ struct SphTest {
 // h > 0 and c >= 0 (|h| >= 2^-350): q <= fl(h*h) and sqrt(fl(h*h)) == h, so -h + sqrt(q) <= 0
 // tame: the lower bound 2^-350 in a tame launch, NaN otherwise (no |h| passes; a double threshold
 // keeps the uniform flag out of lane-mask copies)
-__device__ __forceinline__ SphTest sph_test(double h, double c, double tame) {
+template <typename Tm>
+__device__ __forceinline__ SphTest sph_test(double h, double c, Tm tame) {
   SphTest t;
-  t.half = __ballot(!(fabs(h) >= tame)) == 0 ? 1 : 0;
+  if constexpr (kSticky<Tm>) {  // the half-b form whatever |h| is; a lane below the bound is flagged
+    tame.trip(!(fabs(h) >= 0x1.0p-350));
+    t.half = 1;
+  } else {
+    t.half = __ballot(!(fabs(h) >= tame)) == 0 ? 1 : 0;
+  }
   t.h = h;
   if (t.half) {
     t.d = (h * h) - c;
@@ -435,18 +481,18 @@ __device__ __forceinline__ SphTest sph_test(double h, double c, double tame) {
   }
   return t;
 }
-template <typename P>
+template <typename P, typename Tm>
 __device__ __forceinline__ SphTest isect_disc(const P* g, double ox, double oy, double oz, double oo, double dx,
-                                              double dy, double dz, double tame) {
+                                              double dy, double dz, Tm tame) {
   const double cx = g[RTX_G_CX], cy = g[RTX_G_CY], cz = g[RTX_G_CZ];
   const double h = dot3(dx, dy, dz, ox - cx, oy - cy, oz - cz);
   const double c = ((g[RTX_G_CC] + oo) - 2.0 * dot3(cx, cy, cz, ox, oy, oz)) - g[RTX_G_RR];
   return sph_test(h, c, tame);
 }
 // level-0 camera origin: O - C from uniform values, c precomputed on the host (same expressions)
-template <typename P>
+template <typename P, typename Tm>
 __device__ __forceinline__ SphTest isect_disc_cam(const P* g, double ox, double oy, double oz, double dx, double dy,
-                                                  double dz, double tame) {
+                                                  double dz, Tm tame) {
   const double h = dot3(dx, dy, dz, ox - g[RTX_G_CX], oy - g[RTX_G_CY], oz - g[RTX_G_CZ]);
   return sph_test(h, g[RTX_G_C0], tame);
 }
@@ -495,9 +541,9 @@ __device__ __forceinline__ void isect_pair(const SphTest& a, const SphTest& b, F
   }
 }
 // isect (the reference's root or FARAWAY) through the split test
-template <typename P>
+template <typename P, typename Tm>
 __device__ __forceinline__ double isect_t(const P* g, double ox, double oy, double oz, double oo, double dx, double dy,
-                                          double dz, double tame) {
+                                          double dz, Tm tame) {
   double r = FARAWAY;
   isect_one(isect_disc(g, ox, oy, oz, oo, dx, dy, dz, tame), [&](double t, bool v) {
     if (v) r = t;
@@ -771,9 +817,9 @@ __device__ __forceinline__ bool lit_bvh(const cdouble* sc, double qx, double qy,
 
 // Nearest hit of ray (O, D) over all spheres, geometry through
 // the scalar cache. CAM: O is the camera (level 0), using the host-precomputed c.
-template <bool CAM, typename P, typename Wk>
+template <bool CAM, typename P, typename Wk, typename Tm>
 __device__ __forceinline__ void nearest_hit(const P* geo, int nsph, double ox, double oy, double oz, double dx,
-                                            double dy, double dz, double& tmin, int& hit, bool& tie, double tame,
+                                            double dy, double dz, double& tmin, int& hit, bool& tie, Tm tame,
                                             Wk& wk) {
   wk.test(nsph);
   tmin = FARAWAY;
@@ -815,7 +861,12 @@ __device__ __forceinline__ double sin_reduced(double x) {
   const double s = __builtin_fma(r * z, q, r);
   return ((int)n & 1) ? -s : s;
 }
-__device__ __forceinline__ double sin_ref(const cdouble* sc, double x) {
+template <typename Tm = double>
+__device__ __forceinline__ double sin_ref(const cdouble* sc, double x, Tm tame = Tm()) {
+  if constexpr (kSticky<Tm>) {
+    tame.trip(!(sc[RTX_H_SINRED] != 0.0 || fabs(x) <= 0x1.0p20));
+    return sin_reduced(x);
+  }
   // the reduction above when the host bounded every material's phase (RTX_H_SINRED), else
   // wave-uniform: unless some active lane is out of its range (or NaN / inf)
   if (sc[RTX_H_SINRED] != 0.0 || __ballot(!(fabs(x) <= 0x1.0p20)) == 0) return sin_reduced(x);
@@ -920,14 +971,14 @@ struct Hit {
 // Sums of non-negative terms here and in hit_color are fused multiply-adds (one rounding fewer,
 // within an ulp of the term; A/B r5e: C2 -1.6%, C2main -1.4%, C3 -1.2%, C4 -0.6%): none of them
 // decides anything, and none cancels, so the colour moves by at most a few ulp.
-template <typename M>
+template <typename M, typename Tm = double>
 __device__ __forceinline__ double specular(const M* mh, double g, double nx, double ny, double nz, double lx,
-                                           double ly, double lz, double vx, double vy, double vz) {
+                                           double ly, double lz, double vx, double vy, double vz, Tm tame = Tm()) {
   double Lx = lx, Ly = ly, Lz = lz;
-  norm3_unit(Lx, Ly, Lz);  // :278 (normalised a second time; an ulp of L moves a sharp highlight's
+  norm3_unit(Lx, Ly, Lz, tame);  // :278 (normalised a second time; an ulp of L moves a sharp highlight's
                            // D by ~2500 ulp: skipping it put main.py's 1080p frame 6e-10 off, r4s2)
   double Vx = vx, Vy = vy, Vz = vz;
-  norm3_unit(Vx, Vy, Vz);  // :279 (likewise)
+  norm3_unit(Vx, Vy, Vz, tame);  // :279 (likewise)
   double Hx = Lx + Vx, Hy = Ly + Vy, Hz = Lz + Vz;
   {  // :280
     const double dh = dot3(Hx, Hy, Hz, Hx, Hy, Hz);
@@ -969,10 +1020,10 @@ __device__ __forceinline__ double specular(const M* mh, double g, double nx, dou
 // IMG: image textures are handled (the general kernel, and k_render_fast's texturing build for
 // RTX_F_IMAGES launches); the other k_render_fast builds defer every pixel that meets an
 // image-textured sphere and compile no texture lookup (A/B: carrying it cost C2 +3.4%, C2main +7%).
-template <bool IMG = false, typename M>
+template <bool IMG = false, typename M, typename Tm = double>
 __device__ __forceinline__ void hit_color(const M* mh, const cdouble* sc, double dli, double di, int tk, bool lit,
                                           bool weighted, double spec, double va, double Rr, double Rg, double Rb,
-                                          double& cr, double& cg, double& cb) {
+                                          double& cr, double& cg, double& cb, Tm tame = Tm()) {
   const double litf = lit ? 1.0 : 0.0;
   double tr, tg, tb;
   const double tex = mh[RTX_M_TEX];
@@ -1004,7 +1055,7 @@ __device__ __forceinline__ void hit_color(const M* mh, const cdouble* sc, double
   if (igain != 0.0) {
     const double af = fabs(va - 0.5) * 2.0;  // :204
     const double phase = ((af * RTX_PI) * mh[RTX_M_TFT]) * 10.0;  // :208
-    const double ip = sin_ref(sc, phase);  // :211
+    const double ip = sin_ref(sc, phase, tame);  // :211
     const double hs = mh[RTX_M_HS], omhs = mh[RTX_M_1MHS];
     const double r = __builtin_fma(ip, hs, omhs * (1.0 - ip));  // :221
     const double gg = __builtin_fma(ip, omhs, hs * (1.0 - ip));  // :222
@@ -1106,10 +1157,10 @@ __device__ __forceinline__ void min_masked(const G* geo, uint64_t m0, uint64_t m
 // same table (LDS copy or global).
 // mat: a material record replacing sphere h's own (Shader.create on another shape's shader), or null.
 // TREE = false: the scene has no culling tree (fewer than kTreeMinSpheres spheres), compiled out.
-template <bool IMG = false, bool TREE = true, typename T, typename G, typename Wk>
+template <bool IMG = false, bool TREE = true, typename T, typename G, typename Wk, typename Tm>
 __device__ __forceinline__ void shade(const cdouble* sc, const G* geo, const T* tab, int nsph, int h, double ox,
                                       double oy, double oz, double dx, double dy, double dz, double t, Hit& s,
-                                      double tame, Wk& wk, const T* mat = nullptr) {
+                                      Tm tame, Wk& wk, const T* mat = nullptr) {
   const T* gh = tab + h * RTX_GEOM_WORDS;
   const T* mh = mat ? mat : tab + nsph * RTX_GEOM_WORDS + h * RTX_MAT_WORDS;
   const double px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;  // :73
@@ -1118,7 +1169,7 @@ __device__ __forceinline__ void shade(const cdouble* sc, const G* geo, const T* 
   const double ny = (py - gh[RTX_G_CY]) * inv_r;
   const double nz = (pz - gh[RTX_G_CZ]) * inv_r;
   double lx = sc[RTX_H_LIGHT + 0] - px, ly = sc[RTX_H_LIGHT + 1] - py, lz = sc[RTX_H_LIGHT + 2] - pz;
-  norm3(lx, ly, lz);  // :75
+  norm3(lx, ly, lz, tame);  // :75
   const double qx = px + nx * 0.0001, qy = py + ny * 0.0001, qz = pz + nz * 0.0001;  // :77
 
   // _calculate_shadow (:114-128): lit == (t_self == min_j t_j), no light-distance cutoff.
@@ -1150,7 +1201,7 @@ __device__ __forceinline__ void shade(const cdouble* sc, const G* geo, const T* 
         lit = !(anyv && tsh < tself);
       }
     }
-  } else if (!TREE && sc[RTX_H_TAME] != 0.0) {
+  } else if (!TREE && (kSticky<Tm> || sc[RTX_H_TAME] != 0.0)) {  // (the optimistic body: tame launches only)
     // Scenes without a culling tree, tame: the other spheres first, and t_self only when some lane
     // has a valid root (t_self < 2^62 < FARAWAY in a tame scene, so an invalid test never shadows
     // and a lane without a valid root is lit whatever t_self is). lit <=> no valid root strictly
@@ -1242,7 +1293,7 @@ __device__ __forceinline__ void shade(const cdouble* sc, const G* geo, const T* 
       vy = vy * rv;
       vz = vz * rv;
     }
-    if (weighted) spec = specular(mh, g, nx, ny, nz, lx, ly, lz, vx, vy, vz);
+    if (weighted) spec = specular(mh, g, nx, ny, nz, lx, ly, lz, vx, vy, vz, tame);
     if (need_irid) va = clip01(dot3(nx, ny, nz, vx, vy, vz));  // :201
   }
   s.dli = dli;
@@ -1261,10 +1312,12 @@ __device__ __forceinline__ void shade(const cdouble* sc, const G* geo, const T* 
 }
 
 // Reflected direction (shader.py:151): norm(D - (N*2) * (D.N))
-__device__ __forceinline__ void reflect_dir(double& dx, double& dy, double& dz, double nx, double ny, double nz) {
+template <typename Tm = double>
+__device__ __forceinline__ void reflect_dir(double& dx, double& dy, double& dz, double nx, double ny, double nz,
+                                            Tm tame = Tm()) {
   const double dn = dot3(dx, dy, dz, nx, ny, nz);
   double rx = dx - (nx * 2.0) * dn, ry = dy - (ny * 2.0) * dn, rz = dz - (nz * 2.0) * dn;
-  norm3_unit(rx, ry, rz);  // |D| = |N| = 1 up to rounding, so |R| too
+  norm3_unit(rx, ry, rz, tame);  // |D| = |N| = 1 up to rounding, so |R| too
   dx = rx;
   dy = ry;
   dz = rz;
@@ -1283,8 +1336,9 @@ __device__ __forceinline__ int global_row(const Params& p, int lr) {
 }
 
 // get_ray_directions (base.py:123-141) for pixel (col, global row r).
+template <typename Tm = double>
 __device__ __forceinline__ void camera_dir(const cdouble* sc, int col, int r, int W, int H, double& dx, double& dy,
-                                           double& dz) {
+                                           double& dz, Tm tame = Tm()) {
   // np.linspace: i*step + start, last element set to stop exactly
   const double x = (sc[RTX_H_XFIX] != 0.0 && col == W - 1) ? sc[RTX_H_XSTOP]
                                                             : (double)col * sc[RTX_H_XSTEP] + sc[RTX_H_XSTART];
@@ -1293,17 +1347,18 @@ __device__ __forceinline__ void camera_dir(const cdouble* sc, int col, int r, in
   const double vx = x - sc[RTX_H_CAM + 0];
   const double vy = y - sc[RTX_H_CAM + 1];
   const double vz = sc[RTX_H_VZ];
-  const double rr = inv_mag(((vx * vx) + (vy * vy)) + sc[RTX_H_VZ2]);
+  const double rr = inv_mag(((vx * vx) + (vy * vy)) + sc[RTX_H_VZ2], tame);
   dx = vx * rr;
   dy = vy * rr;
   dz = vz * rr;
 }
 
 // the camera ray of pixel (col, local row lr) of the launch's tile
+template <typename Tm = double>
 __device__ __forceinline__ void camera_ray(const Params& p, int col, int lr, double& ox, double& oy, double& oz,
-                                           double& dx, double& dy, double& dz) {
+                                           double& dx, double& dy, double& dz, Tm tame = Tm()) {
   const cdouble* sc = (const cdouble*)p.scene;
-  camera_dir(sc, col, global_row(p, lr), p.width, p.height, dx, dy, dz);
+  camera_dir(sc, col, global_row(p, lr), p.width, p.height, dx, dy, dz, tame);
   ox = sc[RTX_H_CAM + 0];
   oy = sc[RTX_H_CAM + 1];
   oz = sc[RTX_H_CAM + 2];
@@ -1651,25 +1706,36 @@ __device__ __forceinline__ void stat_wave(unsigned long long* st, int word) {
 // k_render_fast<B, LDS, DEEP>
 // ------------------------------------------------------------------------------------------
 
-// One block tile: (bx, by) in camera mode, block bx of 256 rays in explicit-ray mode, 256 entries
-// of in_list in continuation mode. `first`: the block's first tile, whose level-0 nearest-hit test
-// overlaps the LDS staging of the scene table. DEEP (caps above RTX_FAST_MAX_BOUNCES or none): chains
+// One block tile: (bx, by) in camera mode, block bx of 256 rays (64 in the small-scene kernels) in
+// explicit-ray mode, as many entries of in_list in continuation mode. The level-0 nearest-hit test
+// reads the scalar cache only, so the LDS table need not be complete before stage(hit) (fast_tile:
+// the block's barrier on its first tile; small_wave: the wave's own late staging). DEEP (caps above RTX_FAST_MAX_BOUNCES or none): chains
 // still alive at the launch's record level are deferred with a resume record, and the continuation
 // mode exists; the capped instantiations compile none of it.
 // IMG: image-textured spheres are shaded here (the texel lookup compiled in, RTX_F_IMAGES launches)
 // instead of deferred to the general kernel.
 // NSPH > 0: the scene has exactly NSPH spheres, a compile-time count (the timed small-scene kernels,
 // rtx_small.hip: their sphere loops unroll; A/B r6b, C2 -2.7%); 0: p.nsph at run time.
-template <int B, bool LDS, int DEEP, bool STATS, bool TREE, bool BEAM, bool IMG = false, int NSPH = 0>
-__device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool first, const double* lds_tab,
-                                          bool wave_tile = false) {
+// guard: a double (ignored) renders the tile through the guarded helpers and returns false. A Sticky
+// (small_tile, DEEP 0 only) renders it through their unconditional fast cores; if some lane's flag is
+// set after the bounce loop the whole wave returns true, before anything is written or appended: the
+// caller renders the tile again, guarded.
+// stage(hit): called by the whole wave after the level-0 search, before any lane uses the LDS table.
+template <int B, bool LDS, int DEEP, bool STATS, bool TREE, bool BEAM, bool IMG = false, int NSPH = 0,
+          typename Tm, typename Stage>
+__device__ __forceinline__ bool fast_tile_body(const Params& p, int bx, int by, const double* lds_tab,
+                                               bool wave_tile, Tm guard, Stage&& stage) {
+  static_assert(!kSticky<Tm> || (DEEP == 0 && !TREE && !STATS), "the optimistic body: capped, counter-free, TP 0");
   constexpr int FB = fast_block<TREE>();  // threads per block of this instantiation
   const cdouble* sc = (const cdouble*)p.scene;
   const cdouble* geo = sc + RTX_HDR_WORDS;
   const int nsph = NSPH > 0 ? NSPH : p.nsph;
   const int nb = TREE ? huge_tail(sc, nsph) : nsph;  // the beams' tested spheres
   // the half-b sphere test (SphTest): origins the kernel generates itself, in a tame scene
-  const double tame = p.mode != 1 && p.mode != 3 && sc[RTX_H_TAME] != 0.0 ? 0x1.0p-350 : __builtin_nan("");
+  const auto tame = [&] {
+    if constexpr (kSticky<Tm>) return guard;
+    else return p.mode != 1 && p.mode != 3 && sc[RTX_H_TAME] != 0.0 ? 0x1.0p-350 : __builtin_nan("");
+  }();
 
   int64_t i = 0;
   bool active;
@@ -1744,7 +1810,7 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
       ox = rin[0]; oy = rin[1]; oz = rin[2];
       dx = rin[3]; dy = rin[4]; dz = rin[5];
     } else if (cam0) {
-      camera_ray(p, col, lr, ox, oy, oz, dx, dy, dz);  // no division of the pixel index
+      camera_ray(p, col, lr, ox, oy, oz, dx, dy, dz, tame);  // no division of the pixel index
     } else {
       load_ray(p, i, ox, oy, oz, dx, dy, dz);
     }
@@ -1775,10 +1841,12 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
       nearest_hit<false>(geo, nsph, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
     }
   }
-  if constexpr (LDS) {
-    if (first) __syncthreads();
+  stage(hit);
+  // (the optimistic body keeps its inactive lanes, hit < 0, to the verdict: the wave stays whole for
+  // the second pass)
+  if constexpr (!kSticky<Tm>) {
+    if (!active) return false;
   }
-  if (!active) return;
   constexpr bool CL = !DEEP && LDS && TREE && !BEAM;  // colour in LDS (kColourLdsBytes)
   static_assert(!CL || 3 * sizeof(double) * FB == kColourLdsBytes, "colour LDS");
   double* const cl = CL ? const_cast<double*>(lds_tab) + nsph * kSphWords + threadIdx.x : nullptr;
@@ -1837,7 +1905,7 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
       const double* tab = LDS ? (const double*)lds_tab : p.scene + RTX_HDR_WORDS;
       double lr_, lg_, lb_;
       hit_color<IMG>(tab + nsph * RTX_GEOM_WORDS + hit * RTX_MAT_WORDS, sc, s.dli, s.di, s.tk, s.lit, weighted, s.spec,
-                     s.va, 0.0, 0.0, 0.0, lr_, lg_, lb_);
+                     s.va, 0.0, 0.0, 0.0, lr_, lg_, lb_, tame);
       if constexpr (CL) {
         cl[0] = __builtin_fma(thr, lr_, cl[0]);
         cl[FB] = __builtin_fma(thr, lg_, cl[FB]);
@@ -1871,7 +1939,7 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
       thr = (thr * 0.5) * s.g;  // the reflection's weight, (R * 0.5) * g (shader.py:106)
     }
     // the reflected ray becomes the next level (the level's colour is already in cr, cg, cb)
-    reflect_dir(dx, dy, dz, s.nx, s.ny, s.nz);
+    reflect_dir(dx, dy, dz, s.nx, s.ny, s.nz, tame);
     ox = s.qx;
     oy = s.qy;
     oz = s.qz;
@@ -1914,6 +1982,12 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
       stat_add(st, RTX_S_BEAMT, wk.beamt);
     }
   }
+  if constexpr (kSticky<Tm>) {
+    // one verdict per wave: a lane outside some fast core's exact range sends the whole wave to the
+    // guarded body (nothing was written, and a tie is appended only below)
+    if (__ballot(guard.bad) != 0) return true;
+    if (!active) return false;
+  }
   const int64_t io = DEEP == 2 || !TREE ? i : pixel_index(lane_id_fresh());
   if constexpr (CL) {
     cr = cl[0];
@@ -1924,9 +1998,22 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
     // a tie (deep deferrals were appended with their resume record)
     if (!appended) append_deferred(p, deferred_entry(io, p.frame, rays_through, hits_through));
     if (st && !rin) stat_add(st, RTX_S_DEFERRED, 1);
-    return;
+    return false;
   }
   write_out(p, io, cr, cg, cb);
+  return false;
+}
+
+// the culled kernels' tile (and the small-scene continuation pass's): guarded, the block's LDS table
+// staged by k_render_fast and complete at the barrier after the first tile's level-0 search
+template <int B, bool LDS, int DEEP, bool STATS, bool TREE, bool BEAM, bool IMG = false, int NSPH = 0>
+__device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool first, const double* lds_tab,
+                                          bool wave_tile = false) {
+  fast_tile_body<B, LDS, DEEP, STATS, TREE, BEAM, IMG, NSPH>(p, bx, by, lds_tab, wave_tile, 0.0, [&](int) {
+    if constexpr (LDS) {
+      if (first) __syncthreads();
+    }
+  });
 }
 
 // TP: 0 = no culling tree and no persistent launch (scenes below kTreeMinSpheres), 1 = culling tree,
@@ -1936,6 +2023,8 @@ __device__ __forceinline__ void fast_tile(const Params& p, int bx, int by, bool 
 // from their records; its own instantiation, so that the first pass compiles no resume code)
 template <int B, bool LDS, int DEEP, bool STATS, int TP, bool IMG, int NSPH>
 __device__ __forceinline__ void k_render_fast_tiles(const Params& p, const double* lds_tab);
+template <int B, int DEEP, bool STATS, bool IMG, int NSPH>
+__device__ __forceinline__ void small_wave(const Params& p, double* lds_tab);
 
 // WAVES > 0: that many waves/SIMD instead of the rule below (kFwdWavesLarge)
 template <int B, bool LDS, int DEEP, bool STATS = false, int TP = 2, bool IMG = false, int NSPH = 0, int WAVES = 0>
@@ -1952,6 +2041,11 @@ k_render_fast(Params p0) {
   constexpr bool BEAM = TP >= 2;
   extern __shared__ double lds_tab[];
   const Params p = frame_view(p0, blockIdx.z);  // frame of a multi-frame launch (grid z)
+  if constexpr (TP == 0 && DEEP != 2) {  // one-wave blocks with a start-up of their own
+    static_assert(LDS, "the small-scene kernels stage the table in LDS");
+    small_wave<B, DEEP, STATS, IMG, NSPH>(p, lds_tab);
+    return;
+  }
   {
     // a blob that is not a packed scene of p.nsph spheres (the LDS table and every sphere loop are
     // sized by p.nsph): render nothing and flag it (block-uniform, so the persistent launch's
@@ -1962,8 +2056,9 @@ k_render_fast(Params p0) {
       return;
     }
   }
-  if constexpr (LDS) {  // per-lane view of the sphere table: one LDS copy per block (the barrier is
-                        // in fast_tile, after the first tile's level-0 nearest-hit test)
+  if constexpr (LDS) {  // per-lane view of the sphere table: one LDS copy per block (the culled kernels
+                        // and the continuation pass; the barrier is fast_tile's, after the first tile's
+                        // level-0 nearest-hit test. small_wave above stages its own)
     const double* src = p.scene + RTX_HDR_WORDS;
     for (int k = threadIdx.x; k < p.nsph * kSphWords; k += fast_block<TREE>()) {
       // (the beam kernels: geometry word RTX_G_IDX of the copy holds beam_word, see wave_beam)
@@ -2052,6 +2147,142 @@ __device__ __forceinline__ void k_render_fast_tiles(const Params& p, const doubl
   }
   fast_tile<B, LDS, DEEP, STATS, TREE, BEAM, IMG, NSPH>(p, bx, by, true, lds_tab);
   if (STATS && p.tile_cost && (threadIdx.x & 63) == 0)  // the block's time: the slowest of its waves
+    atomicMax(p.tile_cost + tb, (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_entry));
+}
+
+// One wave of a small-scene kernel (TP 0: scenes below kTreeMinSpheres, one wave per block, one
+// 16 x 4 tile or 64 explicit rays per wave; the continuation pass keeps k_render_fast's order).
+//
+// Start-up. A wave lives ~17 k cycles and a third of them render sky only, so the dependent memory
+// round trips before its first f64 instruction count. After the kernarg, everything the prologue
+// needs is requested in one round: the header's magic and sphere count, the tile-order entry, and
+// the wave's share of the sphere table, which stays in registers (at most kSmallStage words a lane)
+// while the level-0 search runs on the scalar cache. The magic check is consumed after those
+// requests (the table read is sized by the caller's p.nsph, as the sphere loops are; it only reads).
+// The table is written to LDS after the level-0 search, and only if some lane hit something: an
+// all-sky wave writes its zeros and ends without waiting for the table.
+//
+// Guards. The counter-free, texture-free capped builds (OPT) render a camera tile of a tame scene
+// through the optimistic body first (Sticky: no ballot or branch per helper) and fall back to the
+// guarded body, today's code, when the wave's verdict says some lane left a fast core's exact range;
+// untamed scenes and explicit-ray launches go straight to the guarded body. The fast cores return
+// their guarded expansions' bits on in-range operands and no lane's value depends on another lane,
+// so the frame is the same either way. The STATS builds have the guarded body only: their counters
+// count a tile once.
+constexpr int kSmallStage = ((kTreeMinSpheres - 1) * kSphWords + 63) / 64;
+template <int B, int DEEP, bool STATS, bool IMG, int NSPH>
+__device__ __forceinline__ void small_wave(const Params& p, double* lds_tab) {
+  static_assert(kFastWavesSmall == 1 && fast_block<false>() == 64, "small_wave: one wave per block");
+  static_assert(DEEP != 2, "the continuation pass is k_render_fast's");
+  const uint64_t t_entry = STATS && p.tile_cost ? __builtin_amdgcn_s_memrealtime() : 0;  // (learning the order)
+  const cdouble* sc = (const cdouble*)p.scene;
+  const double magic = sc[RTX_H_MAGIC], hn = sc[RTX_H_NSPH];
+  // the wave's share of the table: words lane, lane + 64, ...
+  constexpr int NL = NSPH > 0 ? (NSPH * kSphWords + 63) / 64 : kSmallStage;
+  const double* src = p.scene + RTX_HDR_WORDS;
+  const int nw0 = p.nsph * kSphWords;
+  const int lane = threadIdx.x;
+  double tv[NL];
+  if constexpr (kSmallLateStage) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) tv[j] = lane + 64 * j < nw0 ? src[lane + 64 * j] : 0.0;
+  }
+  // One tile per block. Bottom tile rows are dispatched first: they hold the ground and the
+  // spheres, whose pixels run long bounce chains, while sky rows finish at level 0 and so fill the
+  // end of the grid (longest-first order; A/B: C2 -10%). Output does not depend on the order. Blocks
+  // are dispatched in blockIdx order: a host order (camera launches, rtx_render_camera_sched) maps
+  // dispatch slot b to block tile order[b], block tile t being (t % gridDim.x, bottom-up row
+  // t / gridDim.x), and a cost record takes each block's time.
+  uint32_t tb = blockIdx.y * gridDim.x + blockIdx.x;
+  if constexpr (kSmallLateStage) {  // (the kernarg fields the tile needs further down, in the batch of the ones needed here)
+    const uint32_t gy = gridDim.y;
+    asm volatile("" ::"s"(p.tile_div), "s"(gy), "s"(p.n), "s"(p.part_run), "s"(p.out), "s"(p.no_general));
+  }
+  if (p.tile_order) tb = ((const uint32_t __attribute__((address_space(4)))*)p.tile_order)[tb];
+  // ... and the header words of the camera ray (camera_dir reads the same addresses: these loads serve
+  // it) and of the guard choice. The empty statement takes all of them as scalar operands, so they are
+  // requested together and waited for once, here, with the table loads in flight. (The linspace stop
+  // words are left to camera_dir, whose last column and row alone read them: with them here the
+  // NSPH 3, B 3 build spills.)
+  if constexpr (kSmallLateStage) {
+    const double htame = sc[RTX_H_TAME], c0 = sc[RTX_H_CAM + 0], c1 = sc[RTX_H_CAM + 1], c2 = sc[RTX_H_CAM + 2];
+    const double x0 = sc[RTX_H_XSTART], x1 = sc[RTX_H_XSTEP], y0 = sc[RTX_H_YSTART], y1 = sc[RTX_H_YSTEP];
+    const double xf = sc[RTX_H_XFIX], yf = sc[RTX_H_YFIX];
+    const double vz = sc[RTX_H_VZ], vz2 = sc[RTX_H_VZ2];
+    if constexpr (NSPH >= 1 && NSPH <= 3) {
+      asm volatile("" ::"s"(magic), "s"(hn), "s"(htame), "s"(tb), "s"(c0), "s"(c1), "s"(c2), "s"(x0), "s"(x1), "s"(y0),
+                   "s"(y1), "s"(xf), "s"(yf), "s"(vz), "s"(vz2));
+    } else {  // (more spheres, or a run-time count: with the camera words held from here these builds spill)
+      asm volatile("" ::"s"(magic), "s"(hn), "s"(htame), "s"(tb));
+    }
+  }
+  // a blob that is not a packed scene of p.nsph spheres: render nothing and flag it
+  if (magic != RTX_MAGIC || hn != (double)p.nsph || (NSPH > 0 && p.nsph != NSPH)) {
+    if (threadIdx.x == 0) atomicOr((uint32_t*)p.ws + RTX_WS_STATUS, (uint32_t)RTX_ST_BAD_SCENE);
+    return;
+  }
+  const int nw = NSPH > 0 ? NSPH * kSphWords : nw0;  // (the check above: p.nsph == NSPH)
+  int bx = blockIdx.x, by = gridDim.y - 1 - blockIdx.y;
+  if (p.tile_order) {
+    if (tb >= gridDim.x * gridDim.y) return;  // (block-uniform: a stale order renders nothing)
+    // tb / gridDim.x without a division: q' = hi32(tb * floor(2^32 / g)) is the quotient or one
+    // below it (tb / g - tb * floor(2^32 / g) / 2^32 < tb / 2^32 < 1), so one correction settles it
+    uint32_t q = __umulhi(tb, p.tile_div), r = tb - q * gridDim.x;
+    if (r >= gridDim.x) {
+      r -= gridDim.x;
+      ++q;
+    }
+    bx = (int)r;
+    by = (int)(gridDim.y - 1 - q);
+  }
+  bool staged = false;  // wave-uniform: the LDS table is complete
+  if constexpr (!kSmallLateStage) {
+    for (int k = lane; k < nw; k += 64) lds_tab[k] = src[k];
+    __syncthreads();
+    staged = true;
+  }
+  auto stage_regs = [&](int hit) {
+    if constexpr (!kSmallLateStage) return;
+    if (nw > 64 * NL) {  // (a run-time count beyond the small scenes': straight from memory)
+      for (int k = lane; k < nw; k += 64) lds_tab[k] = src[k];
+      __syncthreads();
+      staged = true;
+    } else if (__ballot(hit >= 0) != 0) {
+#pragma unroll
+      for (int j = 0; j < NL; ++j)
+        if (lane + 64 * j < nw) lds_tab[lane + 64 * j] = tv[j];
+      __syncthreads();  // (one wave: the lanes' writes before any lane's read)
+      staged = true;
+    }
+  };
+  // (NSPH > 0: every scene below kTreeMinSpheres has a build of its own count, go_ns; the run-time-count
+  // build serves none of them and would spill with two bodies)
+  constexpr bool OPT = kSmallOptimistic && DEEP == 0 && !STATS && !IMG && NSPH > 0;
+  bool redo = true;
+  if constexpr (OPT) {
+    if (p.mode == 0 && sc[RTX_H_TAME] != 0.0) {
+      bool bad = false;
+      redo = fast_tile_body<B, true, DEEP, STATS, false, false, IMG, NSPH>(p, bx, by, lds_tab, false, Sticky{bad},
+                                                                          stage_regs);
+    }
+  }
+  if (redo) {
+    if constexpr (OPT) {  // the cold body: the table again from memory unless the first pass staged it
+      // (through a scene pointer the compiler cannot connect with the first body's: no header word
+      // stays in a register across the optimistic body for the sake of this one)
+      Params q = p;
+      asm volatile("" : "+s"(q.scene));
+      fast_tile_body<B, true, DEEP, STATS, false, false, IMG, NSPH>(q, bx, by, lds_tab, false, 0.0, [&](int hit) {
+        if (!staged && __ballot(hit >= 0) != 0) {
+          for (int k = lane; k < nw; k += 64) lds_tab[k] = src[k];
+          __syncthreads();
+        }
+      });
+    } else {
+      fast_tile_body<B, true, DEEP, STATS, false, false, IMG, NSPH>(p, bx, by, lds_tab, false, 0.0, stage_regs);
+    }
+  }
+  if (STATS && p.tile_cost && (threadIdx.x & 63) == 0)  // the block's time
     atomicMax(p.tile_cost + tb, (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_entry));
 }
 

@@ -10,7 +10,8 @@ namespace {
 
 template <int B, int DEEP, bool STATS, bool IMG = false, int NSPH = 0>
 hipError_t go(const void* params, dim3 grid, uint32_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-  const Params& p = *static_cast<const Params*>(params);
+  Params p = *static_cast<const Params*>(params);
+  p.tile_div = grid.x > 1 ? (uint32_t)((uint64_t(1) << 32) / grid.x) : 0xFFFFFFFFu;  // small_wave's tile_order division
   rtx_note_launch(B, true, DEEP, STATS, 0, IMG, NSPH, 0, grid, p.n_fetch, p.tile_order != nullptr, lds);
   hipExtLaunchKernelGGL((k_render_fast<B, true, DEEP, STATS, 0, IMG, NSPH>), grid, dim3(fast_block<false>()), lds, s,
                         e0, e1, 0u, p);
