@@ -31,6 +31,9 @@
  *                       <- no counterpart: adaptive anti-aliasing (HipRenderer(samples=k,
  *                          adaptive=True)): which pixels of a plain frame are edges, the k x k sample
  *                          rays of those pixels, and their resolve written back over the frame
+ *   rtx_occlusion       <- no counterpart: ambient occlusion and soft shadows of the primary hit (the
+ *                          reference's dome light is unshadowed, shader.py:98, its PointLight a point):
+ *                          side x side any-hit rays per hit, each the reference's own sphere test
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -62,7 +65,7 @@ extern "C" {
 
 #define RTX_ABI_VERSION 3 /* 2: rtx_resolve_samples; 3: rtx_last_launches, RTX_WS_COUNTER_BYTES */
 /* (rtx_primary_aovs*, rtx_edge_mask, rtx_sample_dirs and rtx_resolve_scatter were added to version 3:
- * new symbols only, nothing that existed changed; so was rtx_camera_rays) */
+ * new symbols only, nothing that existed changed; so were rtx_camera_rays and rtx_occlusion) */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -516,6 +519,58 @@ enum {
 int rtx_camera_rays(const double* cam, const double* lens, int k, int width, int height,
                     int row_block, int n_parts, int part, int part_run, int n_local_rows,
                     double* origins_out, double* dirs_out, void* stream);
+
+/* Occlusion passes (HipRenderer.render_occlusion / trace_occlusion; the reference adds
+ * its dome light unshadowed, shader.py:98, and its point light has no size): a bundle of side x side
+ * any-hit rays from the primary hit of every ray, computed from the id, position and normal passes
+ * rtx_primary_aovs* wrote (so independent of the camera kind and of the tiling). float [n] each:
+ *   ao        the share of side x side cosine-distributed hemisphere rays that meet no shape nearer
+ *             than max_distance; 1.0 on a miss
+ *   soft_lit  the share of side x side points on a disk of radius light_radius around lights[0] that
+ *             pass the reference's shadow test from this hit; 0.0 on a miss, as lit is
+ * All arithmetic is float64 without contraction in the order written. norm is NumpyVector3D.norm
+ * (base.py:61-64), intersect is shape.py:28-51 in the reference expressions; division and square root
+ * are correctly rounded.
+ * Tables, computed on the host (python_ray_tracer_amd/occlusion.py):
+ *   table  double [3][side*side]  hemisphere_table(side): rows 0 and 1 are camera.lens_table(side),
+ *                                 the concentric image of the stratum centres; row 2 is
+ *                                 sqrt(max(0, 1 - (a*a + b*b)))
+ *   rot    double [2][64]         rotation_table(): entry r is (cos phi, sin phi), phi = 2 pi (r + 0.5) / 64
+ * Per-hit rotation: r depends on the bits of P = position[:, i] only, not on a pixel index (a row
+ * tile, an explicit ray and a perspective camera's pixel give the value of the whole frame). With
+ * bx, by, bz the uint64 bit patterns of P:
+ *   w = bx ^ rotl64(by, 21) ^ rotl64(bz, 42);  x = (uint32)(w ^ (w >> 32))
+ *   x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *   r = x & 63;  (cr, sr) = rot[:, r]
+ * Frame around a unit vector n (Duff et al., branch-free; |s + n.z| >= 1, no singular direction):
+ *   s = copysign(1.0, n.z);  a = -1.0 / (s + n.z);  b = (n.x * n.y) * a
+ *   T = (1.0 + ((s * n.x) * n.x) * a,  s * b,  (-s) * n.x)
+ *   B = (b,  s + (n.y * n.y) * a,  -n.y)
+ * For a ray i with 0 <= id[i] < S (any other id is a miss and reads nothing of the blob), N =
+ * normal[:, i], q = P + N * 0.0001 per component (shader.py:77), h = id[i]:
+ *   ao: T, B around N. For sample j with (x, y, z) = table[:, j]:
+ *     xr = x * cr - y * sr;  yr = x * sr + y * cr
+ *     d = norm((T * xr + B * yr) + N * z)                 per component
+ *     occluded iff min_s intersect(s, q, d) < max_distance, over all S shapes including the hit's own
+ *     ao = (float)((side*side - occluded) / (double)(side*side))
+ *   soft_lit: wv = norm(L - P), L = the blob's RTX_H_LIGHT words; T, B around wv. For sample j with
+ *   (a, b) = table[0:2, j]:
+ *     ar = a * cr - b * sr;  br = a * sr + b * cr
+ *     Lj = L + (T * ar + B * br) * light_radius;  l = norm(Lj - P)
+ *     lit iff intersect(h, q, l) == min_s intersect(s, q, l)   (shader.py:126-128, the reference's own
+ *                                                               test, which does not stop at the light)
+ *     soft_lit = (float)(lit_count / (double)(side*side))
+ *   With light_radius = 0 every sample is the reference's shadow ray: soft_lit == lit exactly.
+ * A blob whose magic or sphere count disagrees with n_spheres makes every ray a miss, as in
+ * rtx_primary_aovs. Either output may be NULL: that pass is then neither computed nor stored.
+ * Asynchronous on `stream`; needs no workspace, never allocates, never synchronises. RTX_E_ARG (before
+ * any HIP call) for a null scene, id, position, normal, table or rot, both outputs null, n_spheres
+ * outside 1..RTX_MAX_SPHERES, side outside 1..8, a negative n, a max_distance outside (0, 1e39] or
+ * NaN, or a light_radius that is negative or not finite; n == 0 returns RTX_OK without a launch. */
+enum { RTX_OCC_AO = 1, RTX_OCC_SOFT = 2, RTX_OCC_ALL = 3 };
+int rtx_occlusion(const double* scene, int n_spheres, const int32_t* id, const double* position,
+                  const double* normal, int64_t n, const double* table, int side, const double* rot,
+                  double max_distance, double light_radius, float* ao, float* soft_lit, void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

@@ -17,6 +17,8 @@
 //                     <- no counterpart: the primary hit's intermediates as render passes (depth, id,
 //                        hits, position, normal, albedo, lit; rtx_primary_aovs), for a row tile of the
 //                        camera's frame or for explicit rays
+//   rt::occlusion     <- no counterpart: ambient occlusion and soft shadows of the primary hit, side x side
+//                        any-hit rays per hit from the id, position and normal passes (rtx_occlusion)
 //   rt::edge_mask, rt::sample_dirs, rt::resolve_scatter
 //                     <- no counterpart: adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True);
 //                        rtx_edge_mask, rtx_sample_dirs, rtx_resolve_scatter), with the tensor-size checks
@@ -634,6 +636,79 @@ std::tuple<std::optional<at::Tensor>, at::Tensor> camera_rays(const at::Tensor& 
   return {origins, dirs};
 }
 
+// ---- occlusion passes (rtx_occlusion) -------------------------------------------------------------
+// `passes`: a mask of RTX_OCC_* bits; the result holds one float32 [n] tensor per set bit, in bit
+// order (ao, soft_lit). The C ABI takes bare pointers: the tensor sizes are checked here. Returns n.
+// Shared by the kernel and its Meta form.
+int64_t check_occlusion(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& id, const at::Tensor& position,
+                        const at::Tensor& normal, const at::Tensor& table, const at::Tensor& rot,
+                        double max_distance, double light_radius, int64_t passes) {
+  check_scene_shape(scene, n_spheres);
+  TORCH_CHECK(passes > 0 && (passes & ~(int64_t)RTX_OCC_ALL) == 0,
+              "passes must be a non-empty mask of RTX_OCC_* bits (1..", (int)RTX_OCC_ALL, "), got ", passes);
+  TORCH_CHECK(id.scalar_type() == at::kInt && id.dim() == 1, "id must be ", at::kInt, " [n], got ", id.scalar_type(),
+              " ", id.sizes());
+  const int64_t n = id.size(0);
+  TORCH_CHECK(position.scalar_type() == at::kDouble && position.dim() == 2 && position.size(0) == 3 &&
+                  position.size(1) == n,
+              "position must be ", at::kDouble, " [3, n] with n = ", n, ", got ", position.scalar_type(), " ",
+              position.sizes());
+  TORCH_CHECK(normal.scalar_type() == at::kDouble && normal.dim() == 2 && normal.size(0) == 3 && normal.size(1) == n,
+              "normal must be ", at::kDouble, " [3, n] with n = ", n, ", got ", normal.scalar_type(), " ",
+              normal.sizes());
+  TORCH_CHECK(table.scalar_type() == at::kDouble && table.dim() == 2 && table.size(0) == 3,
+              "table must be the hemisphere table: ", at::kDouble, " [3, side*side], got ", table.scalar_type(), " ",
+              table.sizes());
+  int64_t side = 0;
+  while (side * side < table.size(1)) ++side;
+  TORCH_CHECK(side >= 1 && side <= 8 && side * side == table.size(1),
+              "table must hold side*side samples with side in 1..8, got ", table.size(1));
+  TORCH_CHECK(rot.scalar_type() == at::kDouble && rot.dim() == 2 && rot.size(0) == 2 && rot.size(1) == 64,
+              "rot must be the rotation table: ", at::kDouble, " [2, 64], got ", rot.scalar_type(), " ", rot.sizes());
+  TORCH_CHECK(max_distance > 0.0 && max_distance <= 1.0e39, "max_distance must lie in (0, 1e39], got ", max_distance);
+  TORCH_CHECK(light_radius >= 0.0 && light_radius <= 1.7976931348623157e308,
+              "light_radius must be finite and not negative, got ", light_radius);
+  return n;
+}
+
+std::vector<at::Tensor> new_occlusion(const at::Tensor& like, int64_t n, int64_t passes) {
+  std::vector<at::Tensor> out;
+  for (int b = 0; b < 2; ++b)
+    if (passes & (int64_t(1) << b)) out.push_back(at::empty({n}, like.options().dtype(at::kFloat)));
+  return out;
+}
+
+std::vector<at::Tensor> occlusion(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& id,
+                                  const at::Tensor& position, const at::Tensor& normal, const at::Tensor& table,
+                                  const at::Tensor& rot, double max_distance, double light_radius, int64_t passes,
+                                  bool check) {
+  check_gpu(scene, "scene", at::kDouble);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  const struct { const at::Tensor& t; const char* name; at::ScalarType dtype; } in[] = {
+      {id, "id", at::kInt}, {position, "position", at::kDouble}, {normal, "normal", at::kDouble},
+      {table, "table", at::kDouble}, {rot, "rot", at::kDouble}};
+  for (const auto& a : in) {
+    check_gpu(a.t, a.name, a.dtype);
+    check_same_device(scene, a.t, a.name);
+  }
+  const int64_t n = check_occlusion(scene, n_spheres, id, position, normal, table, rot, max_distance, light_radius,
+                                    passes);
+  std::vector<at::Tensor> out = new_occlusion(scene, n, passes);
+  if (check) check_headers(scene, n_spheres);
+  if (n == 0) return out;  // (an empty tensor's pointer may be null)
+  int64_t side = 0;
+  while (side * side < table.size(1)) ++side;
+  float* ptr[2] = {nullptr, nullptr};
+  size_t k = 0;
+  for (int b = 0; b < 2; ++b)
+    if (passes & (int64_t(1) << b)) ptr[b] = out[k++].data_ptr<float>();
+  check_rc(rtx_occlusion(scene.data_ptr<double>(), (int)n_spheres, id.data_ptr<int32_t>(), position.data_ptr<double>(),
+                         normal.data_ptr<double>(), n, table.data_ptr<double>(), (int)side, rot.data_ptr<double>(),
+                         max_distance, light_radius, ptr[0], ptr[1], stream_of(scene)),
+           "rtx_occlusion");
+  return out;
+}
+
 int64_t status(at::Tensor& workspace) {
   check_gpu(workspace, "workspace", at::kByte);
   TORCH_CHECK(workspace.numel() >= RTX_WS_HDR_BYTES, "workspace shorter than its header");
@@ -808,6 +883,14 @@ std::vector<at::Tensor> primary_aovs_rays_meta(const at::Tensor& scene, int64_t 
   return new_aovs(scene, dirs.size(1), passes);
 }
 
+std::vector<at::Tensor> occlusion_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& id,
+                                       const at::Tensor& position, const at::Tensor& normal, const at::Tensor& table,
+                                       const at::Tensor& rot, double max_distance, double light_radius,
+                                       int64_t passes, bool) {
+  return new_occlusion(scene, check_occlusion(scene, n_spheres, id, position, normal, table, rot, max_distance,
+                                              light_radius, passes), passes);
+}
+
 at::Tensor edge_mask_meta(const at::Tensor& color, const at::Tensor& id, const at::Tensor& hits,
                           const at::Tensor& lit, int64_t width, int64_t height, double contrast) {
   check_edge_inputs(color, id, hits, lit, width, height, contrast);
@@ -861,6 +944,8 @@ TORCH_LIBRARY(rt, m) {
         "int part_run, int passes, bool check=True) -> Tensor[]");
   m.def("primary_aovs_rays(Tensor scene, int n_spheres, Tensor origins, Tensor dirs, int passes, "
         "bool check=True) -> Tensor[]");
+  m.def("occlusion(Tensor scene, int n_spheres, Tensor id, Tensor position, Tensor normal, Tensor table, Tensor rot, "
+        "float max_distance, float light_radius, int passes, bool check=True) -> Tensor[]");
   m.def("edge_mask(Tensor color, Tensor id, Tensor hits, Tensor lit, int width, int height, float contrast) -> Tensor");
   m.def("sample_dirs(Tensor sample_scene, int k, int width, int height, Tensor pixels) -> Tensor");
   m.def("resolve_scatter(Tensor samples, int k, Tensor pixels, int width, int height, Tensor(a!) out, "
@@ -893,6 +978,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("resolve_samples", &resolve_samples);
   m.impl("primary_aovs", &primary_aovs);
   m.impl("primary_aovs_rays", &primary_aovs_rays);
+  m.impl("occlusion", &occlusion);
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
@@ -913,6 +999,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("resolve_samples", &resolve_samples);
   m.impl("primary_aovs", &primary_aovs);
   m.impl("primary_aovs_rays", &primary_aovs_rays);
+  m.impl("occlusion", &occlusion);
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
@@ -931,6 +1018,7 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("resolve_samples", &resolve_samples_meta);
   m.impl("primary_aovs", &primary_aovs_meta);
   m.impl("primary_aovs_rays", &primary_aovs_rays_meta);
+  m.impl("occlusion", &occlusion_meta);
   m.impl("edge_mask", &edge_mask_meta);
   m.impl("sample_dirs", &sample_dirs_meta);
   m.impl("resolve_scatter", &resolve_scatter_meta);

@@ -16,6 +16,7 @@ from .base import (
     HipRGBColor,
     HipVector3D,
     HipVectorArray3D,
+    OCC_NAMES,
 )
 from .shader import HipShader, ImageTexture, Texture, TextureChecker
 from .shape import HipSphere, HipTexturedSphere
@@ -32,6 +33,7 @@ __all__ = [
     "ImageTexture",
     "HipVector3D",
     "HipVectorArray3D",
+    "OCC_NAMES",
     "Texture",
     "TextureChecker",
 ]

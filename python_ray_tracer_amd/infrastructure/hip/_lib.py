@@ -110,6 +110,7 @@ EXPORTS = (
     "rtx_sample_dirs",
     "rtx_resolve_scatter",
     "rtx_camera_rays",
+    "rtx_occlusion",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -117,6 +118,11 @@ AOV_DEPTH, AOV_ID, AOV_HITS, AOV_POSITION, AOV_NORMAL, AOV_ALBEDO, AOV_LIT = 1, 
 AOV_ALL = 127
 AOV_PASSES = {"depth": AOV_DEPTH, "id": AOV_ID, "hits": AOV_HITS, "position": AOV_POSITION,
               "normal": AOV_NORMAL, "albedo": AOV_ALBEDO, "lit": AOV_LIT}
+# RTX_OCC_*: the occlusion passes (rtx_occlusion; rt::occlusion's mask), in result order
+OCC_AO, OCC_SOFT = 1, 2
+OCC_ALL = 3
+OCC_PASSES = {"ao": OCC_AO, "soft_lit": OCC_SOFT}
+OCC_MAX_SIDE = 8  # samples per bundle side
 
 TILES_MAX_SLOTS = 4
 TILES_LOOPBACK = 1  # rtx_tiles_create flags
@@ -179,6 +185,8 @@ _SIGS = {
     "rtx_resolve_scatter": (_i32, [_c_void_p, _i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p]),
     "rtx_camera_rays": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p,
                                _c_void_p, _c_void_p]),
+    "rtx_occlusion": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i32, _c_void_p,
+                             ctypes.c_double, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 _lib = None

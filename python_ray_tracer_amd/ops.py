@@ -41,6 +41,15 @@ that device's current HIP stream and returns a new tensor):
   float64 [n], 2 id int32 [n], 4 hits int32 [n], 8 position, 16 normal, 32 albedo float64 [3, n],
   64 lit uint8 [n]; the result is a list with one tensor per set bit, in bit order. A pass that is
   not requested is neither computed nor stored. Need no workspace.
+* ``rt::occlusion(scene, n_spheres, id, position, normal, table, rot, max_distance, light_radius,
+  passes, check=True)`` — the occlusion passes of the primary hits (rtx_occlusion;
+  HipRenderer.render_occlusion / trace_occlusion; contract in include/rtx_hip.h): ``id`` int32 [n],
+  ``position`` and ``normal`` float64 [3, n] as ``rt::primary_aovs`` returns them, ``table`` the device
+  hemisphere table float64 [3, side*side] and ``rot`` the rotation table float64 [2, 64]
+  (``occlusion.hemisphere_table``, ``occlusion.rotation_table``), ``max_distance`` in (0, 1e39],
+  ``light_radius`` >= 0. ``passes`` is a mask of the RTX_OCC_* bits (``_lib.OCC_*``): 1 ao, 2 soft_lit,
+  float32 [n] each; the result is a list with one tensor per set bit, in bit order. An id outside
+  0..n_spheres-1 is a miss (ao 1, soft_lit 0). Every tensor's size is checked. Needs no workspace.
 * ``rt::edge_mask(color, id, hits, lit, width, height, contrast)``, ``rt::sample_dirs(sample_scene,
   k, width, height, pixels)`` and ``rt::resolve_scatter(samples, k, pixels, width, height, out,
   out_kind)`` — the three steps of adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True);
@@ -87,7 +96,7 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "resolve_samples", "primary_aovs", "primary_aovs_rays", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
+       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
        "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
        "comm_unique_id", "comm_init", "comm_destroy", "tiles_create", "tiles_submit", "tiles_finish",
