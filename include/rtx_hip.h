@@ -34,6 +34,9 @@
  *   rtx_occlusion       <- no counterpart: ambient occlusion and soft shadows of the primary hit (the
  *                          reference's dome light is unshadowed, shader.py:98, its PointLight a point):
  *                          side x side any-hit rays per hit, each the reference's own sphere test
+ *   rtx_trace_glass     <- no counterpart (shader.py:143 "TODO: VOIR TRANSMISSION"): raytrace_scene on
+ *                          explicit rays through a scene with solid glass spheres, whose transmitted ray
+ *                          is one more level of the recursion, added after the iridescence term
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -65,7 +68,8 @@ extern "C" {
 
 #define RTX_ABI_VERSION 3 /* 2: rtx_resolve_samples; 3: rtx_last_launches, RTX_WS_COUNTER_BYTES */
 /* (rtx_primary_aovs*, rtx_edge_mask, rtx_sample_dirs and rtx_resolve_scatter were added to version 3:
- * new symbols only, nothing that existed changed; so were rtx_camera_rays and rtx_occlusion) */
+ * new symbols only, nothing that existed changed; so were rtx_camera_rays, rtx_occlusion, and
+ * rtx_trace_glass with rtx_glass_workspace_bytes) */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -571,6 +575,55 @@ enum { RTX_OCC_AO = 1, RTX_OCC_SOFT = 2, RTX_OCC_ALL = 3 };
 int rtx_occlusion(const double* scene, int n_spheres, const int32_t* id, const double* position,
                   const double* normal, int64_t n, const double* table, int side, const double* rot,
                   double max_distance, double light_radius, float* ao, float* soft_lit, void* stream);
+
+/* Transmission (HipRenderer on a scene with a transmissive sphere; the reference marks
+ * the spot, shader.py:143 "TODO: VOIR TRANSMISSION", and stores specular_ior = 1.5 "for glass",
+ * shader.py:51): NumpyRenderer.raytrace_scene (base.py:91-121) on n explicit rays, where
+ * NumpyShader.create adds one more term after the iridescence (shader.py:110),
+ *     color += transmission * transmission_gain        for every hit, lit or not
+ * with transmission = raytrace_scene(O', D', scene) one level deeper, traced only where the reflected
+ * ray could be (level < max_bounces). `glass` is double [2][n_spheres]: row 0 the transmission_gain
+ * of every sphere (finite, >= 0; 0: opaque, the sphere is shaded as before), row 1 its specular_ior
+ * (finite, >= 1 where the gain is not 0); it is not part of the scene blob.
+ * A glass sphere is solid: a ray that meets it from outside is refracted in, crosses the ball and is
+ * refracted out. There are no hits from inside, no internal reflections and no total internal
+ * reflection (by the ball's symmetry the exit angle is the entry angle); shapes overlapping the ball
+ * are ignored along the passage; a ray that meets the surface from inside (D.n >= 0) gets no
+ * transmitted ray. The shadow test is unchanged: a glass ball casts a full shadow.
+ * For a hit of sphere (C, r, ior) by the ray (O, D) at distance t, float64 in this order exactly, no
+ * contraction, division and square root correctly rounded, norm NumpyVector3D.norm (base.py:61-64),
+ * dot products (x*x' + y*y') + z*z' (base.py:34-35), vector expressions per component:
+ *     P = O + D*t;  n = (P - C) * (1.0/r)                          (shader.py:73-74)
+ *     c = D.n;  transmit only if c < 0
+ *     eta = 1.0/ior;  ci = -c;  k = 1.0 - (eta*eta)*(1.0 - ci*ci);  f = eta*ci - sqrt(k)
+ *     T = norm(D*eta + n*f)                                         the ray inside the ball
+ *     m = P - C;  b = T.m;  E = P - T*(2*b)                         the exit point
+ *     u = (E - C) * (1.0/r);  ce = T.u
+ *     ke = max(1.0 - (ior*ior)*(1.0 - ce*ce), 0.0);  g = sqrt(ke) - ior*ce
+ *     O' = E + u*0.0001;  D' = norm(T*ior + u*g)
+ * Which rays exist, what they hit (the nearest shape, ties, base.py:102-119) and is_in_light are the
+ * reference's decisions bit for bit. A pixel's colour is the sum over its tree of shaded hits of
+ * weight * (the hit's colour with a black reflection), the weight (w*0.5)*g down a reflection
+ * (shader.py:106) and w*transmission_gain down a transmission: the terms of the reference's nested
+ * sum, reassociated (a few ulp of the colour, as in every render kernel here).
+ * One lane per ray; each lane keeps a stack of 4*max_bounces + 4 pending rays in the workspace (a ray
+ * tree without ties needs max_bounces + 1). A lane that would need more drops the ray and sets
+ * RTX_ST_STACK_OVERFLOW in the workspace's RTX_WS_STATUS word (sticky: the caller reads and clears
+ * it). The workspace is RTX_WS_HDR_BYTES of header, zeroed once by the caller, and the stacks of a
+ * bounded pool of workers: rtx_glass_workspace_bytes(n, max_bounces) does not grow with n beyond that
+ * pool (0 for arguments rtx_trace_glass refuses).
+ * out / out_kind as rtx_trace_rays (RTX_OUT_*; uint8 [n][3]). A blob whose magic or sphere count
+ * disagrees with n_spheres makes every ray a miss (colour 0). Asynchronous on `stream`, never
+ * allocates, never synchronises. RTX_E_ARG (before any HIP call) for a null scene, glass, origins,
+ * dirs, out or workspace, n_spheres outside 1..RTX_MAX_SPHERES, max_bounces outside
+ * 0..RTX_GLASS_MAX_BOUNCES (the tree has up to 2^(max_bounces+1) rays per pixel: no unbounded form),
+ * a bad out_kind, a negative n or an origin_stride other than 0 or n; RTX_E_WORKSPACE for a workspace
+ * that is too small; n == 0 returns RTX_OK without a launch. */
+enum { RTX_GLASS_MAX_BOUNCES = 8 };
+size_t rtx_glass_workspace_bytes(int64_t n_rays, int max_bounces);
+int rtx_trace_glass(const double* scene, int n_spheres, const double* glass, const double* origins,
+                    int64_t origin_stride, const double* dirs, int64_t n, int max_bounces, void* out,
+                    int out_kind, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

@@ -17,6 +17,8 @@
 //                     <- no counterpart: the primary hit's intermediates as render passes (depth, id,
 //                        hits, position, normal, albedo, lit; rtx_primary_aovs), for a row tile of the
 //                        camera's frame or for explicit rays
+//   rt::trace_glass   <- no counterpart (shader.py:143, "TODO: VOIR TRANSMISSION"): raytrace_scene on explicit rays
+//                        through a scene with solid glass spheres (rtx_trace_glass); allocates its workspace
 //   rt::occlusion     <- no counterpart: ambient occlusion and soft shadows of the primary hit, side x side
 //                        any-hit rays per hit from the id, position and normal passes (rtx_occlusion)
 //   rt::edge_mask, rt::sample_dirs, rt::resolve_scatter
@@ -709,6 +711,58 @@ std::vector<at::Tensor> occlusion(const at::Tensor& scene, int64_t n_spheres, co
   return out;
 }
 
+// ---- transmission (rtx_trace_glass) ---------------------------------------------------------------
+// Shapes and ranges of rt::trace_glass's arguments, shared by the kernel and its Meta form: returns n.
+int64_t check_glass(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass, const at::Tensor& origins,
+                    const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind) {
+  check_scene_shape(scene, n_spheres);
+  TORCH_CHECK(glass.scalar_type() == at::kDouble && glass.dim() == 2 && glass.size(0) == 2 &&
+                  glass.size(1) == n_spheres,
+              "glass must be ", at::kDouble, " [2, n_spheres] (glass.glass_table), got ", glass.scalar_type(), " ",
+              glass.sizes());
+  TORCH_CHECK(dirs.scalar_type() == at::kDouble && dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be ", at::kDouble,
+              " [3, n], got ", dirs.scalar_type(), " ", dirs.sizes());
+  const int64_t n = dirs.size(1);
+  TORCH_CHECK(origins.scalar_type() == at::kDouble &&
+                  ((origins.dim() == 1 && origins.numel() == 3) ||
+                   (origins.dim() == 2 && origins.size(0) == 3 && origins.size(1) == n)),
+              "origins must be ", at::kDouble, " [3] (shared) or [3, n] with n = ", n, ", got ", origins.scalar_type(),
+              " ", origins.sizes());
+  TORCH_CHECK(max_bounces >= 0 && max_bounces <= RTX_GLASS_MAX_BOUNCES, "max_bounces must lie in 0..",
+              (int)RTX_GLASS_MAX_BOUNCES, " (a transmissive scene needs a finite cap), got ", max_bounces);
+  TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA || out_kind == RTX_OUT_U8_HWC,
+              "bad out_kind ", out_kind);
+  return n;
+}
+
+at::Tensor trace_glass(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass, const at::Tensor& origins,
+                       const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind, bool check) {
+  check_gpu(scene, "scene", at::kDouble);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  const struct { const at::Tensor& t; const char* name; } in[] = {{glass, "glass"}, {origins, "origins"}, {dirs, "dirs"}};
+  for (const auto& a : in) {
+    check_gpu(a.t, a.name, at::kDouble);
+    check_same_device(scene, a.t, a.name);
+  }
+  const int64_t n = check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind);
+  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
+  if (check) check_headers(scene, n_spheres);
+  if (n == 0) return out;  // (an empty tensor's pointer may be null)
+  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
+  at::Tensor ws = at::zeros({(int64_t)rtx_glass_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
+  check_rc(rtx_trace_glass(scene.data_ptr<double>(), (int)n_spheres, glass.data_ptr<double>(),
+                           origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
+                           (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(),
+                           stream_of(scene)),
+           "rtx_trace_glass");
+  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
+    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
+    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
+                4 * max_bounces + 4, " pending rays; HipRenderer raises RecursionError)");
+  }
+  return out;
+}
+
 int64_t status(at::Tensor& workspace) {
   check_gpu(workspace, "workspace", at::kByte);
   TORCH_CHECK(workspace.numel() >= RTX_WS_HDR_BYTES, "workspace shorter than its header");
@@ -891,6 +945,12 @@ std::vector<at::Tensor> occlusion_meta(const at::Tensor& scene, int64_t n_sphere
                                               light_radius, passes), passes);
 }
 
+at::Tensor trace_glass_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass,
+                            const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                            bool) {
+  return new_output(scene, check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
+}
+
 at::Tensor edge_mask_meta(const at::Tensor& color, const at::Tensor& id, const at::Tensor& hits,
                           const at::Tensor& lit, int64_t width, int64_t height, double contrast) {
   check_edge_inputs(color, id, hits, lit, width, height, contrast);
@@ -946,6 +1006,8 @@ TORCH_LIBRARY(rt, m) {
         "bool check=True) -> Tensor[]");
   m.def("occlusion(Tensor scene, int n_spheres, Tensor id, Tensor position, Tensor normal, Tensor table, Tensor rot, "
         "float max_distance, float light_radius, int passes, bool check=True) -> Tensor[]");
+  m.def("trace_glass(Tensor scene, int n_spheres, Tensor glass, Tensor origins, Tensor dirs, int max_bounces, "
+        "int out_kind, bool check=True) -> Tensor");
   m.def("edge_mask(Tensor color, Tensor id, Tensor hits, Tensor lit, int width, int height, float contrast) -> Tensor");
   m.def("sample_dirs(Tensor sample_scene, int k, int width, int height, Tensor pixels) -> Tensor");
   m.def("resolve_scatter(Tensor samples, int k, Tensor pixels, int width, int height, Tensor(a!) out, "
@@ -979,6 +1041,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("primary_aovs", &primary_aovs);
   m.impl("primary_aovs_rays", &primary_aovs_rays);
   m.impl("occlusion", &occlusion);
+  m.impl("trace_glass", &trace_glass);
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
@@ -1000,6 +1063,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("primary_aovs", &primary_aovs);
   m.impl("primary_aovs_rays", &primary_aovs_rays);
   m.impl("occlusion", &occlusion);
+  m.impl("trace_glass", &trace_glass);
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
@@ -1019,6 +1083,7 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("primary_aovs", &primary_aovs_meta);
   m.impl("primary_aovs_rays", &primary_aovs_rays_meta);
   m.impl("occlusion", &occlusion_meta);
+  m.impl("trace_glass", &trace_glass_meta);
   m.impl("edge_mask", &edge_mask_meta);
   m.impl("sample_dirs", &sample_dirs_meta);
   m.impl("resolve_scatter", &resolve_scatter_meta);

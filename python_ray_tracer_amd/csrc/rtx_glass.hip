@@ -1,0 +1,276 @@
+// rtx_glass.hip — transmission (rtx_trace_glass): explicit rays through a scene in which some spheres
+// are solid glass. A ray that meets such a sphere from outside is refracted in, crosses the ball and
+// is refracted out; the ray that leaves is traced like any other, one more level of raytrace_scene
+// (the reference marks the spot: shader.py:143 "TODO: VOIR TRANSMISSION"). Every hit adds
+// transmission * transmission_gain after the iridescence term (shader.py:110), lit or not. The
+// arithmetic of the passage is written out in include/rtx_hip.h; DESIGN.md §14 has the rest. A
+// translation unit of its own over the shared device text (rtx_device.h), like rtx_occlusion.hip: the
+// render kernels compile from untouched text with untouched flags.
+#include "rtx_device.h"
+#include "rtx_internal.h"
+
+namespace {
+
+constexpr int kRayWords = 8;  // a pending ray: origin, direction, weight, level
+// Pending-ray stacks live in the workspace, kRayWords * glass_stack_entries(B) words per worker; the
+// pool of workers is bounded by this budget and by kGlassMaxWorkers, whatever the ray count (the
+// general kernel's rule, kStackBudget / workers_for)
+constexpr size_t kGlassStackBudget = size_t(256) << 20;
+// 3,072 waves: the 3 per SIMD its 146 VGPRs allow on a 256-CU part, all resident (A/B against 131,072 workers,
+// two alternating pairs, glass_spec 1080p: B = 3 176.4 -> 146.5 us, B = 5 269.0 -> 231.9 us)
+constexpr int64_t kGlassMaxWorkers = 196608;
+// waves per SIMD the kernel is compiled for (A/B against 4, which takes 127 VGPRs and spills 4, with 262,144
+// workers: B = 3 -2.8%, B = 5 +2.9%)
+constexpr int kGlassWaves = 3;
+// The stacks in LDS instead ([entry][word][lane], 4 KB per entry and wave), an A/B switch (tools/ab_build.py
+// --set): caps up to 3 only (16 entries are the 64 KB a block may ask for), two waves per CU. Measured
+// 2.7x slower at B = 3 (profiles/glass_ab.json): the product keeps the stacks in the workspace.
+constexpr bool kGlassLdsStack = false;
+
+__host__ __device__ constexpr int glass_stack_entries(int B) { return 4 * B + 4; }
+
+int64_t glass_workers(int64_t n, int B) {
+  const int64_t per = (int64_t)glass_stack_entries(B) * kRayWords * 8;
+  int64_t w = (int64_t)(kGlassStackBudget / (size_t)per) / 64 * 64;
+  if (w > kGlassMaxWorkers) w = kGlassMaxWorkers;
+  const int64_t need = (n + 63) / 64 * 64;
+  return need < w ? need : w;
+}
+
+struct GlassParams {
+  const double* scene;
+  int nsph;
+  const double* glass;  // [2][nsph]: transmission_gain, specular_ior
+  const double* org;
+  int64_t org_stride;
+  const double* dir;
+  int64_t n;
+  int max_bounces;
+  void* out;
+  int out_kind;
+  uint32_t* status;  // the workspace's RTX_WS_STATUS word
+  double* stack;
+  int64_t n_workers;
+};
+
+// The lane's stack of pending rays, lane-interleaved like the general kernel's Stack: word f of entry
+// e of 64 consecutive workers is one contiguous run.
+struct RayStack {
+  double* base;
+  int64_t nw;
+  int64_t w;
+  __device__ __forceinline__ double& at(int e, int f) const {
+    if constexpr (kGlassLdsStack) {
+      extern __shared__ double lds_stack[];
+      return lds_stack[(e * kRayWords + f) * 64 + threadIdx.x];
+    } else {
+      return base[((int64_t)e * kRayWords + f) * nw + w];
+    }
+  }
+  __device__ __forceinline__ void push(int e, double ox, double oy, double oz, double dx, double dy, double dz,
+                                       double wt, int level) const {
+    at(e, 0) = ox; at(e, 1) = oy; at(e, 2) = oz;
+    at(e, 3) = dx; at(e, 4) = dy; at(e, 5) = dz;
+    at(e, 6) = wt;
+    at(e, 7) = (double)level;
+  }
+};
+
+// The ray that leaves a solid glass ball (centre C, 1/radius inv_r, index ior) which the ray D met
+// from outside at P with normal n and c = D.n < 0: refracted in at P, straight across, refracted out
+// at E. No total internal reflection: by the ball's symmetry the exit angle is the entry angle.
+__device__ __forceinline__ void through_ball(double px, double py, double pz, double dx, double dy, double dz,
+                                             double nx, double ny, double nz, double c, double cx, double cy,
+                                             double cz, double inv_r, double ior, double& ox, double& oy, double& oz,
+                                             double& rx, double& ry, double& rz) {
+  const double eta = div_cr(1.0, ior);
+  const double ci = -c;
+  const double k = 1.0 - (eta * eta) * (1.0 - ci * ci);
+  const double f = eta * ci - sqrt_cr(k);
+  double tx = dx * eta + nx * f, ty = dy * eta + ny * f, tz = dz * eta + nz * f;
+  norm3(tx, ty, tz);
+  const double b = dot3(tx, ty, tz, px - cx, py - cy, pz - cz);
+  const double b2 = 2.0 * b;
+  const double ex = px - tx * b2, ey = py - ty * b2, ez = pz - tz * b2;  // the exit point
+  const double ux = (ex - cx) * inv_r, uy = (ey - cy) * inv_r, uz = (ez - cz) * inv_r;
+  const double ce = dot3(tx, ty, tz, ux, uy, uz);
+  const double ke = max0(1.0 - (ior * ior) * (1.0 - ce * ce));
+  const double g = sqrt_cr(ke) - ior * ce;
+  ox = ex + ux * 0.0001;
+  oy = ey + uy * 0.0001;
+  oz = ez + uz * 0.0001;
+  rx = tx * ior + ux * g;
+  ry = ty * ior + uy * g;
+  rz = tz * ior + uz * g;
+  norm3(rx, ry, rz);
+}
+
+// One lane per ray item; a bounded pool of workers loops over the items. A lane walks its ray tree
+// with a stack of pending rays and a forward-folded weight (the general kernel's sum, trace_general):
+// every shaded hit adds weight * (its colour with a black reflection), and pushes the reflected ray
+// with weight (w * 0.5) * g and the transmitted ray with weight w * gain. The lanes of a wave that
+// need a new ray pop and search together (the search loops are wave-uniform, the sphere table comes
+// through the scalar cache); a lane at a tie (several shapes at the nearest distance, base.py:102-119)
+// shades them one per round in scene order.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kGlassWaves, kGlassWaves)))
+void k_trace_glass(GlassParams p) {
+  const int64_t w = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (w >= p.n_workers) return;
+  const cdouble* sc = (const cdouble*)p.scene;
+  // a blob that is not a packed scene of p.nsph spheres: every ray a miss
+  const int nsph = (sc[RTX_H_MAGIC] == RTX_MAGIC && sc[RTX_H_NSPH] == (double)p.nsph) ? p.nsph : 0;
+  const cdouble* geo = sc + RTX_HDR_WORDS;
+  const double* tab = p.scene + RTX_HDR_WORDS;
+  const double* mtab = tab + nsph * RTX_GEOM_WORDS;
+  const int B = p.max_bounces;
+  const int cap = glass_stack_entries(B);
+  const bool tree = sc[RTX_H_NNODES] != 0.0 && nsph >= kGeneralTreeMin;
+  const double nan = __builtin_nan("");  // the reference expressions in every sphere test (SphTest)
+  const RayStack S{p.stack, p.n_workers, w};
+  Params po{};  // what write_out reads
+  po.out = p.out;
+  po.out_kind = p.out_kind;
+  po.n = p.n;
+  for (int64_t i = w; i < p.n; i += p.n_workers) {
+    {
+      const int64_t s = p.org_stride;
+      const int64_t j = s ? i : 0;
+      S.push(0, p.org[j], p.org[s + j + (s ? 0 : 1)], p.org[2 * s + j + (s ? 0 : 2)], p.dir[i], p.dir[p.n + i],
+             p.dir[2 * p.n + i], 1.0, 0);
+    }
+    int sp = 1;  // pending rays
+    double ar = 0.0, ag = 0.0, ab = 0.0;
+    // the ray whose hits are being shaded: `left` of them to go, the next one at or after shape `next`
+    double ox = 0.0, oy = 0.0, oz = 0.0, dx = 0.0, dy = 0.0, dz = 0.0, oo = 0.0, wt = 0.0, tmin = FARAWAY;
+    int level = 0, left = 0, next = 0;
+    for (;;) {
+      int h = nsph;
+      if (left == 0) {
+        if (sp == 0) break;
+        --sp;
+        ox = S.at(sp, 0); oy = S.at(sp, 1); oz = S.at(sp, 2);
+        dx = S.at(sp, 3); dy = S.at(sp, 4); dz = S.at(sp, 5);
+        wt = S.at(sp, 6);
+        level = (int)S.at(sp, 7);
+        oo = dot3(ox, oy, oz, ox, oy, oz);
+        // the nearest distance (base.py:97-98), how many shapes share it and the first in scene order
+        tmin = FARAWAY;
+        int nh = 0, first = nsph;
+        if (tree) {
+          nearest_count_bvh(sc, ox, oy, oz, oo, dx, dy, dz, tmin, nh, first);
+        } else {
+          for (int s = 0; s < nsph; ++s) {
+            const cdouble* g = geo + __builtin_amdgcn_readfirstlane(s) * RTX_GEOM_WORDS;
+            isect_one(isect_disc(g, ox, oy, oz, oo, dx, dy, dz, nan),
+                      [&](double t, bool v) { count_update(v, t, s, tmin, nh, first); });
+          }
+        }
+        left = tmin != FARAWAY ? nh : 0;  // (nearest != FARAWAY) & (t == nearest), base.py:102-103
+        if (left == 0) continue;
+        h = first;
+      } else {  // a tie: the next shape in scene order at the nearest distance
+        for (int s = next; s < nsph; ++s) {
+          if (isect(tab + s * RTX_GEOM_WORDS, ox, oy, oz, oo, dx, dy, dz) == tmin) {
+            h = s;
+            break;
+          }
+        }
+        if (h == nsph) {  // (cannot happen: `left` counted it)
+          left = 0;
+          continue;
+        }
+      }
+      next = h + 1;
+      --left;
+      Hit s;
+      Work<false> nowk;
+      shade<true>(sc, geo, tab, nsph, h, ox, oy, oz, dx, dy, dz, tmin, s, nan, nowk);
+      const bool weighted = s.lit && s.g != 0.0;
+      double xr, xg, xb;
+      hit_color<true>(mtab + h * RTX_MAT_WORDS, sc, s.dli, s.di, s.tk, s.lit, weighted, s.spec, s.va, 0.0, 0.0, 0.0,
+                      xr, xg, xb);
+      ar = __builtin_fma(wt, xr, ar);
+      ag = __builtin_fma(wt, xg, ag);
+      ab = __builtin_fma(wt, xb, ab);
+      if (level >= B) continue;  // the next level is black
+      if (weighted) {  // the reflected ray, (R * 0.5) * g (shader.py:106)
+        if (sp < cap) {
+          double rx = dx, ry = dy, rz = dz;
+          reflect_dir(rx, ry, rz, s.nx, s.ny, s.nz);
+          S.push(sp, s.qx, s.qy, s.qz, rx, ry, rz, (wt * 0.5) * s.g, level + 1);
+          ++sp;
+        } else {
+          atomicOr(p.status, (uint32_t)RTX_ST_STACK_OVERFLOW);
+        }
+      }
+      const double tg = p.glass[h];
+      if (tg != 0.0) {
+        const double c = dot3(dx, dy, dz, s.nx, s.ny, s.nz);
+        if (c < 0.0) {  // met from outside (a hit from inside gets no transmitted ray)
+          if (sp < cap) {
+            const double* gh = tab + h * RTX_GEOM_WORDS;
+            const double px = ox + dx * tmin, py = oy + dy * tmin, pz = oz + dz * tmin;  // :73, as shade has it
+            double qx, qy, qz, rx, ry, rz;
+            through_ball(px, py, pz, dx, dy, dz, s.nx, s.ny, s.nz, c, gh[RTX_G_CX], gh[RTX_G_CY], gh[RTX_G_CZ],
+                         gh[RTX_G_INVR], p.glass[nsph + h], qx, qy, qz, rx, ry, rz);
+            S.push(sp, qx, qy, qz, rx, ry, rz, wt * tg, level + 1);
+            ++sp;
+          } else {
+            atomicOr(p.status, (uint32_t)RTX_ST_STACK_OVERFLOW);
+          }
+        }
+      }
+    }
+    write_out(po, i, ar, ag, ab);
+  }
+}
+
+}  // namespace
+
+extern "C" size_t rtx_glass_workspace_bytes(int64_t n_rays, int max_bounces) {
+  if (n_rays < 0 || max_bounces < 0 || max_bounces > RTX_GLASS_MAX_BOUNCES) return 0;
+  return (size_t)RTX_WS_HDR_BYTES +
+         (size_t)glass_workers(n_rays, max_bounces) * glass_stack_entries(max_bounces) * kRayWords * 8;
+}
+
+extern "C" int rtx_trace_glass(const double* scene, int n_spheres, const double* glass, const double* origins,
+                               int64_t origin_stride, const double* dirs, int64_t n, int max_bounces, void* out,
+                               int out_kind, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!scene) return rtx_fail(RTX_E_ARG, "null scene pointer");
+  if (!glass) return rtx_fail(RTX_E_ARG, "null glass table pointer");
+  if (!origins || !dirs) return rtx_fail(RTX_E_ARG, "null ray pointer (origins, dirs)");
+  if (!out) return rtx_fail(RTX_E_ARG, "null output pointer");
+  if (!workspace) return rtx_fail(RTX_E_ARG, "null workspace pointer");
+  if (n_spheres < 1 || n_spheres > RTX_MAX_SPHERES) return rtx_fail(RTX_E_ARG, "n_spheres out of range");
+  if (max_bounces < 0 || max_bounces > RTX_GLASS_MAX_BOUNCES)
+    return rtx_fail(RTX_E_ARG, "max_bounces out of range (0..%d): a transmissive scene needs a finite cap",
+                    (int)RTX_GLASS_MAX_BOUNCES);
+  if (out_kind != RTX_OUT_F32_SOA && out_kind != RTX_OUT_F64_SOA && out_kind != RTX_OUT_U8_HWC)
+    return rtx_fail(RTX_E_ARG, "bad out_kind %d", out_kind);
+  if (n < 0) return rtx_fail(RTX_E_ARG, "negative ray count");
+  if (origin_stride != 0 && origin_stride != n)
+    return rtx_fail(RTX_E_ARG, "origin_stride must be 0 (a shared origin) or n");
+  const size_t need = rtx_glass_workspace_bytes(n, max_bounces);
+  if (workspace_bytes < need)
+    return rtx_fail(RTX_E_WORKSPACE, "workspace too small: %zu < %zu bytes (rtx_glass_workspace_bytes)",
+                    workspace_bytes, need);
+  if (n == 0) return RTX_OK;
+  GlassParams p{};
+  p.scene = scene;
+  p.nsph = n_spheres;
+  p.glass = glass;
+  p.org = origins;
+  p.org_stride = origin_stride;
+  p.dir = dirs;
+  p.n = n;
+  p.max_bounces = max_bounces;
+  p.out = out;
+  p.out_kind = out_kind;
+  p.status = (uint32_t*)workspace + RTX_WS_STATUS;
+  p.stack = (double*)((uint8_t*)workspace + RTX_WS_HDR_BYTES);
+  p.n_workers = glass_workers(n, max_bounces);
+  const size_t lds = kGlassLdsStack ? (size_t)glass_stack_entries(max_bounces) * kRayWords * 64 * 8 : 0;
+  if (lds > 65536) return rtx_fail(RTX_E_ARG, "the LDS-stack build traces caps up to 3, got %d", max_bounces);
+  hipLaunchKernelGGL(k_trace_glass, dim3((unsigned)(p.n_workers / 64)), dim3(64), (unsigned)lds, (hipStream_t)stream, p);
+  return rtx_launched("k_trace_glass");
+}

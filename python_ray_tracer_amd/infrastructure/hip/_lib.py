@@ -32,6 +32,7 @@ FAST_MAX_BOUNCES = 6
 UNBOUNDED_LEVELS = 333
 MAX_SPHERES = 1024
 MAX_SAMPLES = 8  # samples per pixel side (rtx_resolve_samples)
+GLASS_MAX_BOUNCES = 8  # the largest bounce cap of a transmissive scene (rtx_trace_glass)
 MAGIC = 5527384.0
 UNBOUNDED = -1
 
@@ -111,6 +112,8 @@ EXPORTS = (
     "rtx_resolve_scatter",
     "rtx_camera_rays",
     "rtx_occlusion",
+    "rtx_glass_workspace_bytes",
+    "rtx_trace_glass",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -187,6 +190,9 @@ _SIGS = {
                                _c_void_p, _c_void_p]),
     "rtx_occlusion": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i32, _c_void_p,
                              ctypes.c_double, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p]),
+    "rtx_glass_workspace_bytes": (_size, [_i64, _i32]),
+    "rtx_trace_glass": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p, _i32,
+                               _c_void_p, _size, _c_void_p]),
 }
 
 _lib = None

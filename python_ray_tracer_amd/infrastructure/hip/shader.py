@@ -5,7 +5,9 @@ On this backend a shader is a parameter record: ``HipRenderer`` packs its fields
 per hit; ``HipShader.create`` itself runs that evaluation for a caller-given batch of hits
 (``rtx_shade_hits``). The constructor signature, defaults and the four hard-wired physical constants
 (``specular_ior=1.5``, ``thin_film_weight=0.1``, ``thin_film_thickness=0.3``, ``thin_film_ior=1.4``,
-``shader.py:51-54``) match the reference, and are writable like there.
+``shader.py:51-54``) match the reference, and are writable like there. ``transmission_gain`` (default
+0.0, writable likewise) is this backend's own: other than 0 it makes the sphere solid glass
+(``python_ray_tracer_amd/glass.py``).
 """
 
 from __future__ import annotations
@@ -88,6 +90,9 @@ class HipShader(Shader):
         self.thin_film_weight = 0.1
         self.thin_film_thickness = 0.3
         self.thin_film_ior = 1.4
+        # not in the reference (shader.py:143, "TODO: VOIR TRANSMISSION"): other than 0, the sphere is solid
+        # glass of index specular_ior and every hit adds transmission * transmission_gain (glass.py)
+        self.transmission_gain = 0.0
 
     def create(self, shape, scene, ray_origin, normalized_ray_direction, distance, ray_tracer=None):
         """NumpyShader.create (shader.py:63-112) on the GPU: the colour of the rays (origin,

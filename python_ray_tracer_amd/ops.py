@@ -50,6 +50,14 @@ that device's current HIP stream and returns a new tensor):
   ``light_radius`` >= 0. ``passes`` is a mask of the RTX_OCC_* bits (``_lib.OCC_*``): 1 ao, 2 soft_lit,
   float32 [n] each; the result is a list with one tensor per set bit, in bit order. An id outside
   0..n_spheres-1 is a miss (ao 1, soft_lit 0). Every tensor's size is checked. Needs no workspace.
+* ``rt::trace_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind, check=True)`` —
+  raytrace_scene on explicit rays through a scene with solid glass spheres (rtx_trace_glass; contract in
+  include/rtx_hip.h): ``glass`` is the device side table float64 [2, n_spheres]
+  (``glass.glass_table``: transmission gains, indices of refraction), origins [3] (shared) or [3, n],
+  ``max_bounces`` in 0..8; out_kind 0 = float32 [3, n], 1 = float64 [3, n], 2 = uint8 [n, 3]. The op
+  allocates its own workspace. With ``check=True`` it reads the status word back (a synchronisation) and
+  raises "maximum recursion depth exceeded" for a ray tree that overflowed a lane's stack of pending
+  rays. Every tensor's dtype, device, contiguity and size is checked.
 * ``rt::edge_mask(color, id, hits, lit, width, height, contrast)``, ``rt::sample_dirs(sample_scene,
   k, width, height, pixels)`` and ``rt::resolve_scatter(samples, k, pixels, width, height, out,
   out_kind)`` — the three steps of adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True);
@@ -96,7 +104,7 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
+       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
        "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
        "comm_unique_id", "comm_init", "comm_destroy", "tiles_create", "tiles_submit", "tiles_finish",

@@ -22,6 +22,7 @@ Spec layout::
                              "iridescence_gain": .., "diffuse_gain": ..,
                              "texture": {"kind": "const" | "checker", "color": [r, g, b]}}}],
                   (or {"kind": "image", "texels": (H, W, 3) float colours} — ImageTexture)
+                  (a shader may also carry "transmission_gain" and "specular_ior": glass, glass_spec)
      "lights": [{"kind": "point", "position": [x, y, z]},
                 {"kind": "dome", "intensity": i, "color": [r, g, b]}],
      "camera": {"position": [x, y, z], "width": W, "height": H}}
@@ -91,6 +92,16 @@ def readme_spec(width: int = 1920, height: int = 1080) -> dict:
         ],
         "camera": {"position": [0, 0.2, -2], "width": int(width), "height": int(height)},
     }
+
+
+def glass_spec(width: int = 1920, height: int = 1080) -> dict:
+    """The README scene with the small sphere made of glass (``transmission_gain`` 0.9, ``diffuse_gain``
+    0.1) and the large one half glass (``transmission_gain`` 0.5): the transmission frame of
+    tools/glass_bench.py and the README. Both keep the default index of refraction, 1.5."""
+    spec = readme_spec(width, height)
+    spec["spheres"][1]["shader"].update(transmission_gain=0.9, diffuse_gain=0.1)
+    spec["spheres"][0]["shader"].update(transmission_gain=0.5)
+    return spec
 
 
 def random_spec(n_spheres: int, seed: int = 0, width: int = 3840, height: int = 2160) -> dict:
@@ -210,6 +221,9 @@ def build_scene(spec: dict):
             texture = Texture(HipRGBColor(*tex["color"]))
         shader = HipShader(sh["reflection_gain"], sh["specular_gain"], sh["specular_roughness"],
                            sh["iridescence_gain"], sh["diffuse_gain"], texture)
+        for key in ("transmission_gain", "specular_ior"):  # optional: glass (glass_spec)
+            if key in sh:
+                setattr(shader, key, sh[key])
         shapes.append(HipSphere(HipVector3D(*s["center"]), s["radius"], shader))
     lights = []
     for li in spec["lights"]:
