@@ -119,6 +119,52 @@ def trace(scene, gains, iors, origin, dirs, max_bounces, counts=None, level=0):
     return col
 
 
+def pending_need(scene, gains, iors, origin, dirs, max_bounces, level=0):
+    """Per ray, the largest number of pending rays that k_trace_glass's depth-first walk would hold with
+    an unbounded stack (the kernel's holds 4 * max_bounces + 4; a lane that needs more drops rays and
+    reports RTX_ST_STACK_OVERFLOW). Arguments as ``trace``; an int64 array, at least 1: the ray itself.
+
+    The walk pops a ray and, for every shape at the nearest distance in scene order, when level <
+    max_bounces, pushes the reflected ray (``lit and specular_gain != 0``) and then the transmitted one
+    (``gain != 0 and c < 0``); it pops the last pushed first and finishes that ray's whole tree before the
+    next. So the j-th ray a node pushed (from 0) is popped with j siblings still below it, and a node
+    needs max(1, max_j (j + need of its j-th child)) entries, itself included: the recursion below,
+    vectorised over the rays of a call like ``trace`` and built from the same pieces."""
+    dx, dy, dz = (np.asarray(d, dtype=np.float64) for d in dirs)
+    ox, oy, oz = origin
+    n = dx.shape[0]
+    need = np.ones(n, dtype=np.int64)
+    if level >= max_bounces or n == 0:  # the next level is black: nothing is pushed
+        return need
+    dist = [O.intersect(sp, ox, oy, oz, dx, dy, dz) for sp in scene.spheres]
+    nearest = reduce(np.minimum, dist)
+    pushed = np.zeros(n, dtype=np.int64)
+
+    def push(rays, o2, d2):  # the child rays of the rays ``rays`` (indices into this call's)
+        child = pending_need(scene, gains, iors, o2, d2, max_bounces, level + 1)
+        need[rays] = np.maximum(need[rays], pushed[rays] + child)
+        pushed[rays] += 1
+
+    for si, (sp, d) in enumerate(zip(scene.spheres, dist)):
+        hit = (nearest != O.FARAWAY) & (d == nearest)
+        if not np.any(hit):
+            continue
+        idx = np.nonzero(hit)[0]
+        sub = (lambda a: a if np.ndim(a) == 0 else a[idx])  # noqa: E731
+        hx, hy, hz, hdx, hdy, hdz, ht = sub(ox), sub(oy), sub(oz), dx[idx], dy[idx], dz[idx], d[idx]
+        m = idx.shape[0]
+        _, _, lit, _, q, r = O._shade(scene, si, sp, hx, hy, hz, hdx, hdy, hdz, ht)
+        refl = np.broadcast_to(lit & (sp.specular_gain != 0), (m,))
+        if refl.any():
+            push(idx[refl], tuple(np.broadcast_to(c, (m,))[refl] for c in q), tuple(c[refl] for c in r))
+        if gains[si] != 0:
+            cdn, o2, d2 = through_ball(sp, iors[si], hx, hy, hz, hdx, hdy, hdz, ht)
+            go = cdn < 0
+            if go.any():
+                push(idx[go], tuple(c[go] for c in o2), tuple(c[go] for c in d2))
+    return need
+
+
 def scene_of(spec, gains, iors=None):
     """(the oracle's scene of ``spec``, gains, iors) as ``trace`` takes them: ``iors`` default to 1.5
     each (shader.py:51) and are the shaders' specular_ior (the specular's F0 reads it too, shader.py:290)."""

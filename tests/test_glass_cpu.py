@@ -4,7 +4,10 @@ The C ABI entries and their host-side argument checks, the rt::trace_glass op (s
 TORCH_CHECKs), the side table and every host refusal of glass.py, build_scene's two optional shader
 keys, the restatement (tests/glass_ref.py) pinned to the oracle bit for bit at zero gain, and the
 preconditions that keep the GPU cases of tests/test_gpu_glass.py meaningful: how many rays each case
-sends through glass and how many pixels of its uint8 frame that changes.
+sends through glass and how many pixels of its uint8 frame that changes. For the cases of
+tests/test_gpu_glass_limits.py also how many pending rays the kernel's walk holds (G.pending_need)
+against the 4B + 4 its stack has, how much glass a frame larger than the pool of workers puts among
+the workers' second items, and how many exits of the grazing rays take the clamp.
 """
 
 import ctypes
@@ -47,6 +50,12 @@ CASES = {
     "fuzz3": (lambda: specs.fuzz_spec(3), _all(0.7), 3, 940, 468, 61),  # the camera inside a glass ball
     "fuzz15": (lambda: specs.fuzz_spec(15), _all(0.7), 3, 476, 0, 5),
     "ties": (_ties_spec, _all(0.8), 2, 2798, 0, 357),  # 251 rays with two shapes at the nearest distance (226 at level 0)
+    # the ends of the cap range: 0 (nothing is pushed), 1, 7 and 8 (36 stack entries, the budget-limited pool of
+    # workers); the 65-sphere scenes take the culling-tree search, and reach levels 7 and 8 (the README scene stops at 6)
+    "cap0": (lambda: scenes.readme_spec(32, 18), _all(0.8), 0, 0, 0, 0),  # the opaque frame
+    "cap1": (lambda: scenes.random_spec(16, 1, 48, 27), _all(0.8), 1, 589, 0, 41),
+    "cap7": (lambda: scenes.random_spec(64, 2, 48, 27), _all(0.8), 7, 2276, 79, 332),
+    "cap8": (lambda: scenes.random_spec(64, 2, 48, 27), _all(0.8), 8, 2318, 83, 332),
 }
 
 _frames: dict = {}
@@ -65,6 +74,118 @@ def frame(key):
         changed = int((O.to_uint8(col, W, H) != O.to_uint8(plain, W, H)).any(axis=-1).sum())
         _frames[key] = (spec, gains, cap, col, counts, changed)
     return _frames[key]
+
+
+def _changed_mask(a, b, W, H):
+    """Per pixel: does the uint8 frame of ``a`` differ from that of ``b``."""
+    return (O.to_uint8(a, W, H) != O.to_uint8(b, W, H)).any(axis=-1).reshape(-1)
+
+
+def frame_need(spec, gains, cap, iors=None):
+    """G.pending_need of the frame of ``spec``: per pixel, the pending-ray stack an unbounded walk holds."""
+    osc, g, iors = G.scene_of(spec, gains, iors)
+    d = O.ray_directions(osc.cam, osc.width, osc.height)
+    return G.pending_need(osc, g, iors, tuple(float(c) for c in osc.cam), d, cap)
+
+
+# ---- the pending-ray stack at its capacity (tests/test_gpu_glass_limits.py) ----------------------------------
+
+def coincident_spec(k, matt=0):
+    """tie_spec's construction (tests/golden/make_golden.py) with k coincident spheres instead of two,
+    at 32x18: sphere 1 of the README scene another k - 1 times at index 2, each copy with a constant
+    texture of its own and specular_gain 0.6. Every ray that hits one of them is at a k-way tie, and
+    with every gain at 0.8 a lit camera ray there pushes 2k rays at B = 1, into a stack of 8. The first
+    ``matt`` copies (the last of the tie in scene order) get specular_gain 0.0 instead: no reflected
+    ray, one push less each."""
+    spec = scenes.readme_spec(32, 18)
+    for j in range(k - 1):
+        dup = json.loads(json.dumps(spec["spheres"][1]))
+        dup["shader"]["texture"] = {"kind": "const", "color": [0.1 + 0.2 * j, 0.9 - 0.2 * j, 0.2 + 0.1 * j]}
+        dup["shader"]["specular_gain"] = 0.6 if j >= matt else 0.0
+        spec["spheres"].insert(2, dup)
+    return spec
+
+
+_stacks: dict = {}
+
+
+def stack_case(k, matt=0):
+    """(spec, gains, the restatement's frame at B = 1, its counts, the opaque frame, pending_need per
+    pixel) of coincident_spec(k, matt) with every gain 0.8, computed once."""
+    if (k, matt) not in _stacks:
+        spec = coincident_spec(k, matt)
+        gains = [0.8] * len(spec["spheres"])
+        counts = G.Counts()
+        col = G.render(spec, gains, None, 1, counts=counts)
+        _stacks[(k, matt)] = (spec, gains, col, counts, O.render(O.scene_from_spec(spec), 1), frame_need(spec, gains, 1))
+    return _stacks[(k, matt)]
+
+
+# ---- frames larger than the pool of workers (a worker's second item) -----------------------------------------
+
+def pool(cap):
+    """The largest pool of workers rtx_trace_glass launches at ``cap``, from the library's own workspace
+    size: the workspace of a huge ray count holds one stack of 4 cap + 4 rays of 64 bytes per worker."""
+    return (int(L.load().rtx_glass_workspace_bytes(1 << 40, cap)) - L.WS_HDR_BYTES) // ((4 * cap + 4) * 64)
+
+
+# key -> (spec, gains, cap, changed uint8 pixels among the pixels [pool:], the workers' second items). Both
+# frames' second laps reach the spheres (640x360 at B = 3 and 480x270 at B = 8 have ground there only: 0).
+LAPS = {
+    "lap_B3": (lambda: scenes.readme_spec(800, 450), [0.9, 0.9, 0.0], 3, 11025),  # 360,000 rays, a pool of 196,608
+    "lap_B8": (lambda: scenes.readme_spec(640, 360), [0.9, 0.9, 0.0], 8, 9554),  # 230,400 rays, a pool of 116,480
+}
+_laps: dict = {}
+
+
+def lap_frame(key):
+    """(spec, gains, cap, the restatement's frame, the opaque frame, the pool at this cap), computed once.
+    Fails, never skips, when the pool was retuned and the frame no longer ends in the second lap."""
+    if key not in _laps:
+        make, gains, cap = LAPS[key][:3]
+        spec = make()
+        n, p = spec["camera"]["width"] * spec["camera"]["height"], pool(cap)
+        assert p < n < 2 * p, (f"{key}: {n} rays do not end in the second lap of a pool of {p} workers: the pool was "
+                               f"retuned, pick another frame (and re-measure LAPS)")
+        _laps[key] = (spec, gains, cap, G.render(spec, gains, None, cap), O.render(O.scene_from_spec(spec), cap), p)
+    return _laps[key]
+
+
+# ---- grazing rays: the limb of a glass ball, where the exit's max(..., 0) is taken ---------------------------
+
+GRAZING_RAYS = 200000
+# (sphere of the README scene, its specular_ior) -> exits clamped over the whole trace at B = 2 (through_ball
+# alone, on every hit of the sphere, clamps 57 / 1,809 / 10,446 of 178,088 and 36 / 745 / 3,895 of 189,473; the
+# trace sends 156,796 and 189,473 rays through glass)
+GRAZING = {(0, 1.5): 57, (0, 2.4): 1615, (0, 10.0): 9175, (1, 1.5): 36, (1, 2.4): 745, (1, 10.0): 3895}
+_grazing: dict = {}
+
+
+def grazing_rays(si):
+    """Parallel rays (0, 0, 1) from z = cz - 5 past the limb of sphere ``si`` of the README scene: impact
+    parameter r (1 - eps), eps log-uniform in [1e-16, 1e-6], azimuth uniform. (origins, dirs), 3 arrays each."""
+    s = scenes.readme_spec(32, 18)["spheres"][si]
+    (cx, cy, cz), r, n = (float(v) for v in s["center"]), float(s["radius"]), GRAZING_RAYS
+    rng = np.random.default_rng(1)
+    eps = 10.0 ** rng.uniform(-16.0, -6.0, n)
+    phi = rng.uniform(0.0, 2.0 * np.pi, n)
+    b = r * (1.0 - eps)
+    return ((cx + b * np.cos(phi), cy + b * np.sin(phi), np.full(n, cz - 5.0)), (np.zeros(n), np.zeros(n), np.ones(n)))
+
+
+def grazing_case(si, ior):
+    """(spec with the gains, gains, iors, origins, dirs, the restatement's colours at B = 2, its counts) for
+    sphere ``si`` made of glass of index ``ior`` with gain 0.9, the others opaque; computed once."""
+    if (si, ior) not in _grazing:
+        gains, iors = [0.0] * 3, [1.5] * 3
+        gains[si], iors[si] = 0.9, ior
+        spec = scenes.readme_spec(32, 18)  # (the rays are the caller's: the frame size is not used)
+        osc, g, io = G.scene_of(spec, gains, iors)
+        o, d = grazing_rays(si)
+        counts = G.Counts()
+        col = np.stack(G.trace(osc, g, io, o, d, 2, counts=counts))
+        _grazing[(si, ior)] = (G.with_gains(spec, gains, iors), gains, iors, o, d, col, counts)
+    return _grazing[(si, ior)]
 
 
 def test_header_declares_and_library_exports_the_entries():
@@ -258,6 +379,109 @@ def test_preconditions_of_the_gpu_cases(key):
     assert counts.deepest == cap and np.isfinite(col).all()
     if key == "ties":  # rays with two shapes at the nearest distance: 226 camera rays, 251 over the three levels
         assert (counts.ties0, counts.ties) == (226, 251)
+
+
+def _walked_need(osc, gains, iors, origin, d, cap):
+    """pending_need of one ray by the kernel's walk taken literally: a stack of (origin, direction,
+    level), pop one, push its rays shape by shape, and the high-water mark of the stack."""
+    one = (lambda v: np.array([v], dtype=np.float64))  # noqa: E731
+    stack = [(tuple(one(c) for c in origin), tuple(one(c) for c in d), 0)]
+    high = 1
+    while stack:
+        o, dr, level = stack.pop()
+        if level >= cap:
+            continue
+        dist = [O.intersect(sp, *o, *dr) for sp in osc.spheres]
+        nearest = min(float(t[0]) for t in dist)
+        if nearest == O.FARAWAY:
+            continue
+        for si, sp in enumerate(osc.spheres):
+            if float(dist[si][0]) != nearest:
+                continue
+            _, _, lit, _, q, r = O._shade(osc, si, sp, *o, *dr, dist[si])
+            if bool(np.all(lit)) and sp.specular_gain != 0:
+                stack.append((q, r, level + 1))
+            if gains[si] != 0:
+                c, o2, d2 = G.through_ball(sp, iors[si], *o, *dr, dist[si])
+                if c[0] < 0:
+                    stack.append((o2, d2, level + 1))
+            high = max(high, len(stack))
+    return high
+
+
+def test_pending_need_is_the_walk_taken_literally():
+    """The vectorised recursion of G.pending_need against a scalar stack machine, ray by ray, on the two
+    frames with ties: five coincident spheres at B = 1 and the golden tie spec at B = 2 (every fourth ray)."""
+    for spec, gains, cap, step in ((coincident_spec(5), [0.8] * 7, 1, 1), (_ties_spec(), [0.8] * 4, 2, 4)):
+        osc, g, iors = G.scene_of(spec, gains)
+        cam = tuple(float(c) for c in osc.cam)
+        d = np.stack(O.ray_directions(osc.cam, osc.width, osc.height))[:, ::step]
+        need = G.pending_need(osc, g, iors, cam, tuple(d), cap)
+        walked = [_walked_need(osc, g, iors, cam, d[:, i], cap) for i in range(d.shape[1])]
+        assert need.tolist() == walked
+        assert max(walked) > cap + 1  # the ties are in the sample
+
+
+def test_pending_need_without_and_with_ties():
+    for cap in (3, 8):  # no ties: a depth-first walk holds at most one sibling per level
+        need = frame_need(scenes.readme_spec(32, 18), [0.9, 0.9, 0.0], cap)
+        assert need.min() == 1 and need.max() == 3 <= cap + 1
+    spec, gains, cap = frame("ties")[:3]
+    need = frame_need(spec, gains, cap)
+    assert need.max() == 5 <= 4 * cap + 4  # the 5 of DESIGN.md §14
+    assert np.bincount(need).tolist() == [0, 918, 951, 201, 116, 118]
+
+
+@pytest.mark.parametrize("key", ["cap0", "cap1", "cap7", "cap8"])
+def test_the_ends_of_the_cap_range_fit_the_stack(key):
+    spec, gains, cap = frame(key)[:3]
+    need = frame_need(spec, gains, cap)
+    print(f"{key}: the walk holds up to {need.max()} pending rays of {4 * cap + 4}")
+    assert need.max() == {"cap0": 1, "cap1": 2, "cap7": 7, "cap8": 7}[key] <= 4 * cap + 4
+    if key == "cap0":  # nothing is transmitted: the opaque frame, bit for bit
+        assert np.array_equal(frame(key)[3], O.render(O.scene_from_spec(spec), 0))
+
+
+def test_preconditions_of_the_stack_at_capacity():
+    """Four coincident spheres fill the 8 entries of B = 1 exactly on 53 pixels; a fifth overflows them
+    on the same 53 and on no other: by 2 entries, or, when it sends no reflected ray, by exactly 1."""
+    for k, matt, transmitted, changed, full in ((4, 0, 520, 57, 8), (5, 0, 573, 54, 10), (5, 1, 573, 55, 9)):
+        spec, gains, col, counts, plain, need = stack_case(k, matt)
+        moved = int(_changed_mask(col, plain, 32, 18).sum())
+        print(f"k = {k}, {matt} matt: {counts}, {moved} uint8 pixels changed, need {np.bincount(need).tolist()}")
+        assert len(spec["spheres"]) == k + 2 and np.isfinite(col).all()
+        assert (counts.transmitted, counts.ties0, counts.ties, counts.deepest, moved) == (transmitted, 53, 55, 1, changed)
+        hist = [0] * (full + 1)
+        hist[1], hist[2], hist[full] = 231, 292, 53  # rays that push at most one ray, two, and the lit k-way ties
+        assert np.bincount(need).tolist() == hist
+    over = stack_case(5)[5] > 8
+    assert int(over.sum()) == 53 and np.array_equal(over, stack_case(4)[5] == 8)
+    assert np.array_equal(over, stack_case(5, 1)[5] == 9)
+    assert (stack_case(4)[5] <= 8).all()
+
+
+@pytest.mark.parametrize("key", sorted(LAPS))
+def test_preconditions_of_the_second_lap(key):
+    spec, gains, cap, col, plain, p = lap_frame(key)
+    W, H = spec["camera"]["width"], spec["camera"]["height"]
+    moved = _changed_mask(col, plain, W, H)
+    print(f"{key}: pool {p}, {W * H} rays, {int(moved[p:].sum())} of {int(moved.sum())} changed uint8 pixels in lap 2")
+    assert int(moved[p:].sum()) == LAPS[key][3] and np.isfinite(col).all()
+    assert frame_need(spec, gains, cap).max() == 3 <= 4 * cap + 4
+
+
+@pytest.mark.parametrize("case", sorted(GRAZING), ids=lambda c: f"sphere{c[0]}-ior{c[1]}")
+def test_preconditions_of_the_grazing_rays(case):
+    si, ior = case
+    spec, gains, iors, o, d, col, counts = grazing_case(si, ior)
+    osc = G.scene_of(spec, gains, iors)[0]
+    hit = O.intersect(osc.spheres[si], *o, *d) != O.FARAWAY
+    print(f"sphere {si}, ior {ior}: {counts}, {int(hit.sum())} rays hit the sphere")
+    assert int(hit.sum()) == {0: 178088, 1: 189473}[si]  # the others round to a miss
+    assert counts.clamps == GRAZING[case] > 0
+    assert counts.inside == 0 and counts.deepest == 2 and counts.ties == 0 and np.isfinite(col).all()
+    assert counts.transmitted == {0: 156796, 1: 189473}[si]
+    assert G.pending_need(osc, gains, iors, o, d, 2).max() == 2 <= 12
 
 
 def test_rows_of_the_restatement_are_the_rows_of_the_frame():
