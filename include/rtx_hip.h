@@ -127,11 +127,21 @@ enum {
   RTX_H_NBEAM = 41,  /* culled scenes: spheres [NBEAM, S) are all huge (the culling tree's always-tested
                         ones, RTX_H_NALWAYS): the level-0 tile candidates and the reflected-ray beams take
                         them as candidates without a test; 0 = no such tail (older blobs) */
-  RTX_H_SBOX = 42    /* culled scenes of at most 128 spheres: word offset of S records {x lo, x hi, y lo,
+  RTX_H_SBOX = 42,   /* culled scenes of at most 128 spheres: word offset of S records {x lo, x hi, y lo,
                         y hi}, each sphere's image-plane box for this camera: a camera ray through (x, y, 0)
                         outside it provably yields FARAWAY for that sphere (bounds may be infinite);
                         0 = none (the level-0 tile candidates then take the frustum-plane test) */
+  RTX_H_CAMREL = 43  /* scenes of up to 5 spheres: RTX_H_CAMREL + 1, the word offset of S records of
+                        RTX_CAMREL_WORDS words in scene order, {camera.x - cx, camera.y - cy,
+                        camera.z - cz, (RTX_G_C0 >= 0.0) ? 1.0 : 0.0}: the float64 subtractions of the
+                        level-0 sphere test (shape.py:33-34 with the camera as the origin) done once per
+                        (scene, camera). The table fills the header's spare words up to
+                        RTX_HDR_WORDS - 1, so the blob is no longer for it and the header is full; only
+                        there do the small-scene kernels read it. A larger scene's table follows
+                        everything else in the blob (no kernel reads it yet). 0 = none: the kernels
+                        subtract per lane */
 };
+#define RTX_CAMREL_WORDS 4
 #define RTX_MAGIC 5527384.0 /* 'RTX1' */
 #define RTX_SHGRID_WORDS 13 /* words of the shadow-grid record before its masks */
 
@@ -717,6 +727,11 @@ int rtx_tiles_timing(void* plan, int slot, float* gather_ms, float* assemble_ms)
  * render kernels use the fast paths (correctly rounded sequences without operand scaling where it
  * is the identity); tests require each pair to agree bit for bit. */
 int rtx_selftest_math(const double* a, const double* b, int64_t n, double* out, void* stream);
+/* Test hook: out[i] = the render kernels' sine (the reduction and polynomial for |x| <= 2^20, the path
+ * every shade takes when RTX_H_SINRED is set) of x[i], i < n, compiled as the kernels compile it. The
+ * sine is a fixed chain of float64 multiplications and fused multiply-adds, so it is determined bit
+ * for bit (tests/test_gpu_uniform_terms.py evaluates the chain exactly). */
+int rtx_selftest_sin(const double* x, int64_t n, double* out, void* stream);
 
 /* Test hook: the k_render_fast launches of the calling thread's latest render call
  * (rtx_render_camera*, rtx_render_frames, rtx_trace_rays, rtx_shade_hits, rtx_tiles_submit), in

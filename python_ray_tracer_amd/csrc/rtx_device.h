@@ -108,6 +108,20 @@ constexpr bool kSmallOptimistic = true;
 // the sphere table requested with the header words and held in registers until the level-0 search
 // has found a hit (an all-sky wave never waits for it); false: staged in LDS before the tile
 constexpr bool kSmallLateStage = true;
+// Wave-uniform terms kept out of the vector unit, each switch an A/B of its own on identical frames
+// (profiles/uniform_terms_C2.json):
+// the level-0 search of the small-scene kernels takes camera - centre and the sign of the camera's c
+// from the packer's table (RTX_H_CAMREL) instead of three subtractions of scalars per sphere and lane
+constexpr bool kCamRelTable = true;
+// the small-scene kernels' camera ray: a wave whose tile ends before the frame's last column and row
+// (a scalar decision from the tile's position) computes the linspace points without the stop-word
+// selects; the fix words of the others are tested by their bits (f64_nonzero_bits: a scalar test where
+// the compare of doubles is a vector instruction; same verdict for every double). It relies on one
+// wave tile per block (a static_assert in fast_tile_body): set it false to tune kFastWavesSmall
+constexpr bool kCameraStraight = true;
+// (Built, measured and taken out again, profiles/uniform_terms_C2.json: the sine's polynomial with its
+// coefficients as scalar operands of v_fma_f64, and the header's counts read as bit patterns. Neither
+// moved C2's time, and with both the culled kernels, which share shade, lost 0.3-0.6%.)
 // ---- derived ----
 constexpr int kWaveH = 64 / kWaveW;
 static_assert(kFastWaves == 1 || kFastWaves == 2 || kFastWaves == 4, "kFastWaves");
@@ -274,6 +288,16 @@ __device__ __forceinline__ Params frame_view(const Params& p, int f) {
 
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
   return ((ax * bx) + (ay * by)) + (az * bz);  // NumpyVector3D.dot, base.py:34-35
+}
+
+// Wave-uniform header words as bit patterns: gfx9 has no scalar floating point, so a compare of a
+// double that sits in scalar registers is a vector instruction in every lane; its integer reading is
+// scalar.
+__device__ __forceinline__ uint64_t f64_bits(double v) { return (uint64_t)__double_as_longlong(v); }
+// v != 0.0 (true for NaN, false for either zero) by its bits
+// (as two dwords: the compiler turns the 64-bit form back into the compare of doubles)
+__device__ __forceinline__ bool f64_nonzero_bits(double v) {
+  return (((uint32_t)__double2hiint(v) << 1) | (uint32_t)__double2loint(v)) != 0;
 }
 
 // The range-checked helpers below (sph_test, inv_mag, inv_mag_unit, sin_ref and what calls them) take
@@ -481,6 +505,29 @@ __device__ __forceinline__ SphTest sph_test(double h, double c, Tm tame) {
   }
   return t;
 }
+// sph_test with c >= 0.0 decided by the caller (cpos, wave-uniform: the host's verdict on the camera's
+// c, RTX_H_CAMREL) instead of a compare in every lane; everything else as above
+template <typename Tm>
+__device__ __forceinline__ SphTest sph_test_cpos(double h, double c, bool cpos, Tm tame) {
+  SphTest t;
+  if constexpr (kSticky<Tm>) {
+    tame.trip(!(fabs(h) >= 0x1.0p-350));
+    t.half = 1;
+  } else {
+    t.half = __ballot(!(fabs(h) >= tame)) == 0 ? 1 : 0;
+  }
+  t.h = h;
+  if (t.half) {
+    t.d = (h * h) - c;
+    // (no short circuit: the verdict's load then stays with the record's, outside a branch of its own)
+    t.skip = !(t.d > 0.0) | ((h > 0.0) & cpos);
+  } else {
+    const double b = 2.0 * h;
+    t.d = (b * b) - (4.0 * c);
+    t.skip = !(t.d > 0.0) || (b >= 1e-150 && cpos && b <= 1e150);  // behind(b, c)
+  }
+  return t;
+}
 template <typename P, typename Tm>
 __device__ __forceinline__ SphTest isect_disc(const P* g, double ox, double oy, double oz, double oo, double dx,
                                               double dy, double dz, Tm tame) {
@@ -495,6 +542,17 @@ __device__ __forceinline__ SphTest isect_disc_cam(const P* g, double ox, double 
                                                   double dz, Tm tame) {
   const double h = dot3(dx, dy, dz, ox - g[RTX_G_CX], oy - g[RTX_G_CY], oz - g[RTX_G_CZ]);
   return sph_test(h, g[RTX_G_C0], tame);
+}
+// ... and O - C too (r: the sphere's RTX_H_CAMREL record, the host's float64 camera - centre and
+// its verdict on c >= 0.0): h starts at the dot product, with each difference as the multiplication's
+// one scalar operand, and the behind test needs no compare of c
+template <typename Tm>
+__device__ __forceinline__ SphTest isect_disc_rel(const cdouble* g, const cdouble* r, double dx, double dy, double dz,
+                                                  Tm tame) {
+  const double h = dot3(dx, dy, dz, r[0], r[1], r[2]);
+  // the verdict word is 1.0 or 0.0: its high dword alone, so that the test is a 32-bit scalar compare
+  const uint32_t cpos = ((const uint32_t __attribute__((address_space(4)))*)r)[2 * 3 + 1];
+  return sph_test_cpos(h, g[RTX_G_C0], cpos != 0, tame);
 }
 // The rest of the test, as a root and a validity flag instead of the FARAWAY sentinel (no f64
 // selects of a non-inline constant): valid <=> the reference returns the root, not FARAWAY. With
@@ -832,6 +890,33 @@ __device__ __forceinline__ void nearest_hit(const P* geo, int nsph, double ox, d
         return CAM ? isect_disc_cam(g, ox, oy, oz, dx, dy, dz, tame) : isect_disc(g, ox, oy, oz, oo, dx, dy, dz, tame);
       },
       [](const P*, int s) { return s; }, [&](int s, double t, bool v) { nearest_update(v, t, s, tmin, hit, tie); });
+}
+
+// The camera-relative centres of a small scene (RTX_H_CAMREL), or null: a blob without them, or with
+// them elsewhere than in the header's spare words (where the packer puts the table of a scene of up to
+// kCamRelHeaderSpheres spheres), takes the per-lane subtractions. The address is that fixed place, so
+// the table's loads wait for no header word: the header only says whether the table is there. nsph:
+// the blob's checked sphere count.
+constexpr int kCamRelAt = RTX_H_CAMREL + 1;
+constexpr int kCamRelHeaderSpheres = (RTX_HDR_WORDS - kCamRelAt) / RTX_CAMREL_WORDS;
+template <int NSPH>
+__device__ __forceinline__ const cdouble* camrel_table(const cdouble* sc, int nsph) {
+  if constexpr (!kCamRelTable || NSPH > kCamRelHeaderSpheres) return nullptr;
+  if (NSPH == 0 && nsph > kCamRelHeaderSpheres) return nullptr;
+  return f64_bits(sc[RTX_H_CAMREL]) == f64_bits((double)kCamRelAt) ? sc + kCamRelAt : nullptr;
+}
+// nearest_hit<true> with O - C and the sign of c from the table `rel` (camrel_table)
+template <typename Wk, typename Tm>
+__device__ __forceinline__ void nearest_hit_rel(const cdouble* geo, const cdouble* rel, int nsph, double dx, double dy,
+                                                double dz, double& tmin, int& hit, bool& tie, Tm tame, Wk& wk) {
+  static_assert(RTX_GEOM_WORDS == 2 * RTX_CAMREL_WORDS, "a geometry record's offset halves to its table record's");
+  wk.test(nsph);
+  tmin = FARAWAY;
+  hit = -1;
+  tie = false;
+  scan_range(
+      geo, 0, nsph, [&](const cdouble* g) { return isect_disc_rel(g, rel + (g - geo) / 2, dx, dy, dz, tame); },
+      [](const cdouble*, int s) { return s; }, [&](int s, double t, bool v) { nearest_update(v, t, s, tmin, hit, tie); });
 }
 
 // (x)^5 and (x)^2.5 for x in [0, 1] (shader.py:291, :310). NumPy evaluates these with its SIMD pow;
@@ -1352,6 +1437,31 @@ __device__ __forceinline__ void camera_dir(const cdouble* sc, int col, int r, in
   dy = vy * rr;
   dz = vz * rr;
 }
+// camera_dir of the small-scene kernels (kCameraStraight; a function of its own, so that every other
+// caller compiles from unchanged text). inner (wave-uniform): no lane of the wave is in the frame's
+// last column or row, so the linspace stops are not even asked about; the other waves take the selects
+// above with the fix words read by their bits.
+template <typename Tm>
+__device__ __forceinline__ void camera_dir_small(const cdouble* sc, int col, int r, int W, int H, bool inner,
+                                                 double& dx, double& dy, double& dz, Tm tame) {
+  double x, y;
+  if (inner) {
+    x = (double)col * sc[RTX_H_XSTEP] + sc[RTX_H_XSTART];
+    y = (double)r * sc[RTX_H_YSTEP] + sc[RTX_H_YSTART];
+  } else {
+    x = (f64_nonzero_bits(sc[RTX_H_XFIX]) && col == W - 1) ? sc[RTX_H_XSTOP]
+                                                            : (double)col * sc[RTX_H_XSTEP] + sc[RTX_H_XSTART];
+    y = (f64_nonzero_bits(sc[RTX_H_YFIX]) && r == H - 1) ? sc[RTX_H_YSTOP]
+                                                          : (double)r * sc[RTX_H_YSTEP] + sc[RTX_H_YSTART];
+  }
+  const double vx = x - sc[RTX_H_CAM + 0];
+  const double vy = y - sc[RTX_H_CAM + 1];
+  const double vz = sc[RTX_H_VZ];
+  const double rr = inv_mag(((vx * vx) + (vy * vy)) + sc[RTX_H_VZ2], tame);
+  dx = vx * rr;
+  dy = vy * rr;
+  dz = vz * rr;
+}
 
 // the camera ray of pixel (col, local row lr) of the launch's tile
 template <typename Tm = double>
@@ -1810,7 +1920,18 @@ __device__ __forceinline__ bool fast_tile_body(const Params& p, int bx, int by, 
       ox = rin[0]; oy = rin[1]; oz = rin[2];
       dx = rin[3]; dy = rin[4]; dz = rin[5];
     } else if (cam0) {
-      camera_ray(p, col, lr, ox, oy, oz, dx, dy, dz, tame);  // no division of the pixel index
+      if constexpr (kCameraStraight && !TREE) {
+        // a whole-frame launch's tile that ends before the frame's last column and row (so it is not
+        // clipped either): the straight-line camera ray. Row tiles (n_parts > 1) keep the selects.
+        static_assert(WX == 1 && WY == 1, "one wave tile per block: (bx, by) is the wave's tile");
+        const bool inner = p.n_parts == 1 && bx * WW + WW < p.width && by * WH + WH < p.height;
+        camera_dir_small(sc, col, global_row(p, lr), p.width, p.height, inner, dx, dy, dz, tame);
+        ox = sc[RTX_H_CAM + 0];
+        oy = sc[RTX_H_CAM + 1];
+        oz = sc[RTX_H_CAM + 2];
+      } else {
+        camera_ray(p, col, lr, ox, oy, oz, dx, dy, dz, tame);  // no division of the pixel index
+      }
     } else {
       load_ray(p, i, ox, oy, oz, dx, dy, dz);
     }
@@ -1836,7 +1957,10 @@ __device__ __forceinline__ bool fast_tile_body(const Params& p, int bx, int by, 
         nearest_bvh<false>(sc, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
       }
     } else if (cam0) {
-      nearest_hit<true>(geo, nsph, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
+      // (the small-scene kernels: O - C from the packer's table where the blob has it)
+      const cdouble* const rel = TREE ? nullptr : camrel_table<NSPH>(sc, nsph);
+      if (rel) nearest_hit_rel(geo, rel, nsph, dx, dy, dz, tmin, hit, tie, tame, wk);
+      else nearest_hit<true>(geo, nsph, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
     } else {
       nearest_hit<false>(geo, nsph, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
     }
@@ -2209,7 +2333,11 @@ __device__ __forceinline__ void small_wave(const Params& p, double* lds_tab) {
     const double x0 = sc[RTX_H_XSTART], x1 = sc[RTX_H_XSTEP], y0 = sc[RTX_H_YSTART], y1 = sc[RTX_H_YSTEP];
     const double xf = sc[RTX_H_XFIX], yf = sc[RTX_H_YFIX];
     const double vz = sc[RTX_H_VZ], vz2 = sc[RTX_H_VZ2];
-    if constexpr (NSPH >= 1 && NSPH <= 3) {
+    if constexpr (NSPH >= 1 && NSPH <= 3 && kCamRelTable) {  // (... and the word that says whether the table is there)
+      const double crel = sc[RTX_H_CAMREL];
+      asm volatile("" ::"s"(magic), "s"(hn), "s"(htame), "s"(tb), "s"(c0), "s"(c1), "s"(c2), "s"(x0), "s"(x1), "s"(y0),
+                   "s"(y1), "s"(xf), "s"(yf), "s"(vz), "s"(vz2), "s"(crel));
+    } else if constexpr (NSPH >= 1 && NSPH <= 3) {
       asm volatile("" ::"s"(magic), "s"(hn), "s"(htame), "s"(tb), "s"(c0), "s"(c1), "s"(c2), "s"(x0), "s"(x1), "s"(y0),
                    "s"(y1), "s"(xf), "s"(yf), "s"(vz), "s"(vz2));
     } else {  // (more spheres, or a run-time count: with the camera words held from here these builds spill)

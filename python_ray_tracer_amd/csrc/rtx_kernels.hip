@@ -269,6 +269,14 @@ __global__ __launch_bounds__(kBlock) void k_selftest_math(const double* __restri
   out[5 * n + i] = 1.0 / (x == 0.0 ? 1.0 : __builtin_sqrt(x));
 }
 
+// the render kernels' sine (sin_reduced) on a list of phases
+__global__ __launch_bounds__(kBlock) void k_sin_reduced(const double* __restrict__ x, int64_t n,
+                                                        double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  out[i] = sin_reduced(x[i]);
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_quantize(const T* __restrict__ c, int64_t n, uint8_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -963,6 +971,14 @@ int rtx_selftest_math(const double* a, const double* b, int64_t n, double* out, 
   hipLaunchKernelGGL(k_selftest_math, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                      (hipStream_t)stream, a, b, n, out);
   return check_launch("k_selftest_math");
+}
+
+int rtx_selftest_sin(const double* x, int64_t n, double* out, void* stream) {
+  if (!x || !out) return rtx_fail(RTX_E_ARG, "null pointer argument");
+  if (n <= 0) return RTX_OK;
+  hipLaunchKernelGGL(k_sin_reduced, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                     x, n, out);
+  return check_launch("k_sin_reduced");
 }
 
 int rtx_quantize_u8(const void* color, int color_kind, int64_t n, uint8_t* out, void* stream) {

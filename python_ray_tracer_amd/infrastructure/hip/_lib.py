@@ -59,6 +59,8 @@ H_YSTART, H_YSTEP, H_YSTOP, H_YFIX = 24, 25, 26, 27
 H_VZ, H_VZ2, H_W, H_H, H_CAMOO = 28, 29, 30, 31, 32
 H_NNODES, H_NALWAYS, H_NODES, H_CGEO, H_TAME, H_MAT0, H_SHGRID, H_SINRED, H_NBEAM, H_SBOX = (
     33, 34, 35, 36, 37, 38, 39, 40, 41, 42)
+H_CAMREL = 43  # word offset of the camera-relative centres (CAMREL_WORDS per sphere), 0: none
+CAMREL_WORDS = 4
 SIN_TFT_MAX = 2.0 ** 20 / (10.0 * 3.141592653589793 * 1.001)  # thin-film thickness bound of RTX_H_SINRED
 SHGRID_WORDS = 13
 TAME_BOUND = 2.0 ** 60
@@ -89,6 +91,7 @@ EXPORTS = (
     "rtx_profile_collect",
     "rtx_profile_sample",
     "rtx_selftest_math",
+    "rtx_selftest_sin",
     "rtx_assemble_rows",
     "rtx_shade_hits",
     "rtx_assemble_runs",
@@ -157,6 +160,7 @@ _SIGS = {
     "rtx_profile_collect": (_i32, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i32)]),
     "rtx_profile_sample": (_i32, [_i32]),
     "rtx_selftest_math": (_i32, [_c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p]),
+    "rtx_selftest_sin": (_i32, [_c_void_p, _i64, _c_void_p, _c_void_p]),
     "rtx_shade_hits": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _c_void_p,
                               _i32, _c_void_p, _size, _c_void_p, _c_void_p]),
     "rtx_assemble_rows": (_i32, [_c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p]),

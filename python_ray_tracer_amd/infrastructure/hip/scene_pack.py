@@ -192,6 +192,17 @@ def _pack_static(static: tuple) -> np.ndarray:
         blob[L.HDR_WORDS + S * L.GEOM_WORDS + s_idx * L.MAT_WORDS + L.M_TR] = offsets[ref.digest]
     if textures:
         blob = np.concatenate([blob] + [t.ravel() for t in textures])
+    # camera-relative centres (RTX_H_CAMREL), filled by _apply_camera. Up to CAMREL_HEADER_SPHERES
+    # spheres: in the header's spare words, where the small-scene kernels read them (the blob keeps its
+    # length). More: after everything else, so that no other offset moves (no kernel reads it there
+    # yet: the culled kernels and the six- and seven-sphere builds subtract per lane); a blob's texel
+    # tables stay its last words, so a larger textured scene carries none
+    if CAMREL_TABLE and S <= CAMREL_HEADER_SPHERES:
+        blob[L.H_CAMREL] = L.H_CAMREL + 1
+    elif CAMREL_TABLE and not textures:
+        off = blob.size
+        blob = np.concatenate([blob, np.zeros(S * L.CAMREL_WORDS)])
+        blob[L.H_CAMREL] = off
     blob.setflags(write=False)
     return blob
 
@@ -281,9 +292,27 @@ def _apply_camera(blob: np.ndarray, cpos, W: int, H: int) -> None:
         co = (geo[:, L.G_CX] * ox + geo[:, L.G_CY] * oy) + geo[:, L.G_CZ] * oz
         geo[:, L.G_C0] = ((geo[:, L.G_CC] + cw["oo"]) - 2 * co) - geo[:, L.G_RR]
     h[L.H_TAME] = 1.0 if is_tame(tables[0].reshape(S, L.GEOM_WORDS), cpos) else 0.0
+    if h[L.H_CAMREL]:
+        # O - C of the level-0 sphere test (shape.py:33-34 with the camera as the origin): the float64
+        # subtraction the kernel would do in every lane, and its verdict on c >= 0
+        off = int(h[L.H_CAMREL])
+        geo = tables[0].reshape(S, L.GEOM_WORDS)
+        rel = blob[off: off + S * L.CAMREL_WORDS].reshape(S, L.CAMREL_WORDS)
+        rel[:, 0:3] = np.asarray(cpos, dtype=np.float64)[None, :] - geo[:, L.G_CX:L.G_CZ + 1]
+        rel[:, 3] = np.where(geo[:, L.G_C0] >= 0.0, 1.0, 0.0)
     if h[L.H_SBOX]:
         off = int(h[L.H_SBOX])
         blob[off: off + 4 * S] = sphere_plane_boxes(tables[0].reshape(S, L.GEOM_WORDS), cpos).ravel()
+
+
+# --- camera-relative centres (RTX_H_CAMREL) ----------------------------------------------------
+# The level-0 sphere test's O - C (shape.py:33-34 with the camera as the origin) and the sign of its c,
+# per sphere. For scenes of up to CAMREL_HEADER_SPHERES spheres the table fills the header's spare
+# words after RTX_H_CAMREL (so the next header word needs a layout change: RTX_HDR_WORDS is full); a
+# larger scene's is appended to a blob without texel tables.
+# False: no table, the header word stays 0 and the kernels subtract per lane.
+CAMREL_TABLE = True
+CAMREL_HEADER_SPHERES = (L.HDR_WORDS - (L.H_CAMREL + 1)) // L.CAMREL_WORDS  # 5
 
 
 # --- image-plane boxes (RTX_H_SBOX) -----------------------------------------------------------

@@ -1,0 +1,223 @@
+"""Wave-uniform terms kept out of the vector unit (rtx_device.h: kCamRelTable, kCameraStraight) change
+no bit of a frame.
+
+The small-scene kernels take ``camera - centre`` and the sign of the camera's ``c`` from the packer's
+table (RTX_H_CAMREL) and compute the camera ray of a wave that holds neither the frame's last column
+nor its last row without the linspace-stop selects. Every case renders its scene four ways:
+
+* a ``learn_tile_order=False`` renderer (counter-free: the optimistic body, the table, the straight
+  camera ray), whose launch record names the build under test;
+* a ``collect_stats=True`` renderer (the STATS build: the guarded body, a run-time sphere count);
+* a default renderer, twice (recording, then with the learnt tile order);
+* the same rays as explicit rays (``raytrace_scene`` on a materialised direction tensor: neither the
+  table nor the camera path, every term computed per lane).
+
+The camera frames must be bit-identical to each other and to the explicit-ray frame, and the plain one
+within 1e-12 of the oracle with identical uint8.
+
+The sine is pinned on its own: ``rtx_selftest_sin`` runs the render kernels' ``sin_reduced`` on 256
+phases, compared bit for bit with the same chain of fused multiply-adds evaluated exactly
+(``fractions.Fraction``, each fused step rounded once): whatever form its steps are compiled in, they
+must round as the chain does."""
+
+import copy
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import numpy_oracle as O
+from python_ray_tracer_amd import scenes
+from python_ray_tracer_amd.tiling import tile_rows
+
+pytestmark = pytest.mark.gpu
+
+ATOL = 1e-12
+
+
+@pytest.fixture(scope="module")
+def hip():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from python_ray_tracer_amd.infrastructure import hip as H
+
+    return H
+
+
+def c1_spec(width, height, position=None):
+    spec, _ = scenes.CONFIGS["C1"]()
+    return scenes.with_camera(spec, position=None if position is None else list(position), width=width, height=height)
+
+
+def counted_spec(n, width, height):
+    """C1's scene (n = 3), or n of seven spheres: C1's two, four small ones, and the ground last
+    (n = 1: the first sphere alone)."""
+    spec = c1_spec(width, height)
+    if n == 3:
+        return spec
+    proto, ground = spec["spheres"][1], spec["spheres"][-1]
+    extra = [dict(copy.deepcopy(proto), center=c, radius=r) for c, r in
+             (([-1.2, 0.0, 2.0], 0.5), ([1.4, -0.2, 1.2], 0.3), ([0.2, 0.9, 2.2], 0.35), ([-0.3, -0.3, 0.2], 0.2))]
+    small = spec["spheres"][:2] + extra
+    spec["spheres"] = small[:1] if n == 1 else small[:n - 1] + [ground]
+    assert len(spec["spheres"]) == n
+    return spec
+
+
+def explicit_frame(H, scene, cap):
+    """The frame of the scene camera's rays handed over as a direction tensor (mode 1)."""
+    r = H.HipRenderer(cap)
+    rays = r.get_ray_directions(scene.camera)
+    assert rays.data.shape[0] == 3  # materialised: raytrace_scene now takes them as explicit rays
+    return r.raytrace_scene(scene.camera.position, rays, scene).data.cpu().numpy()
+
+
+def four_ways(H, spec, cap, small=True):
+    """The module docstring's renders of ``spec`` at bounce cap ``cap``; returns the plain frame."""
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+
+    scene = scenes.build_scene(spec)
+    osc = O.scene_from_spec(spec)
+    W, Hh, S = osc.width, osc.height, len(osc.spheres)
+    want = O.render(osc, cap)
+    label = (S, W, Hh, cap)
+
+    plain = H.HipRenderer(cap, learn_tile_order=False)
+    f_plain = plain.render_tile(scene).cpu().numpy()
+    recs, _ = L.last_launches()
+    if small:  # the build under test: (TP 0, STATS 0, IMG 0, DEEP 0, B cap, NSPH S)
+        assert [(k.TP, k.STATS, k.IMG, k.DEEP, k.B, k.NSPH) for k in recs] == [(0, 0, 0, 0, cap, S)], recs
+    else:  # the culled kernel: a run-time sphere count
+        assert [(k.TP, k.STATS, k.IMG, k.DEEP, k.B, k.NSPH) for k in recs] == [(1, 0, 0, 0, cap, 0)], recs
+    counting = H.HipRenderer(cap, collect_stats=True)
+    f_count = counting.render_tile(scene).cpu().numpy()
+    assert all(k.STATS == 1 for k in L.last_launches()[0])
+    r = H.HipRenderer(cap)
+    twice = [r.render_tile(scene).cpu().numpy() for _ in range(2)]
+    f_rays = explicit_frame(H, scene, cap)
+    for k, f in enumerate([f_count, *twice, f_rays]):
+        assert f.shape == f_plain.shape, (label, "frame", k)
+        assert np.array_equal(f.view(np.uint64), f_plain.view(np.uint64)), (label, "frame", k,
+                                                                            float(np.abs(f - f_plain).max()))
+    err = float(np.abs(f_plain - want).max())
+    assert err <= ATOL, (label, err)
+    assert np.array_equal(O.to_uint8(f_plain, W, Hh), O.to_uint8(want, W, Hh)), label
+    return f_plain
+
+
+@pytest.mark.parametrize("cap", [0, 3])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 6, 7])
+def test_every_sphere_count_clipped_frame(hip, n, cap):
+    """50 x 14: both edges are clipped (16 x 4 wave tiles), and the last column and row, the linspace
+    stops, sit in clipped tiles; the builds of one to five spheres read the table in the header's
+    spare words (six and seven spheres do not fit there and keep the per-lane subtraction)."""
+    four_ways(hip, counted_spec(n, 50, 14), cap)
+
+
+@pytest.mark.parametrize("cap", [0, 3])
+def test_full_tiles_take_the_straight_camera_ray(hip, cap):
+    """48 x 12: no clipped tile; the waves of the last tile column and row hold the stops in full
+    tiles, the four others take the straight-line camera ray."""
+    four_ways(hip, c1_spec(48, 12), cap)
+
+
+def test_row_tiles_own_the_last_row(hip):
+    """50 x 14 in two parts of 4-row blocks: each part equals its rows of the whole frame; the frame's
+    last row (13) is a row of part 1, in a tile whose local rows end before the tile's height."""
+    W, Hh = 50, 14
+    spec = c1_spec(W, Hh)
+    scene = scenes.build_scene(spec)
+    whole = four_ways(hip, spec, 3).reshape(3, Hh, W)
+    seen = []
+    for part in (0, 1):
+        rows = tile_rows(Hh, 4, 2, part)
+        r = hip.HipRenderer(3, learn_tile_order=False)
+        got = r.render_tile(scene, row_block=4, n_parts=2, part=part).cpu().numpy().reshape(3, len(rows), W)
+        assert np.array_equal(got.view(np.uint64), whole[:, rows, :].view(np.uint64)), part
+        seen += list(rows)
+    assert sorted(seen) == list(range(Hh)) and Hh - 1 in tile_rows(Hh, 4, 2, 1)
+
+
+def test_camera_inside_a_sphere(hip):
+    """The camera inside C1's large sphere: c < 0 for it, so its verdict word is 0 and the behind test
+    never skips it, while the other spheres keep theirs."""
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+    from python_ray_tracer_amd.infrastructure.hip import scene_pack as P
+
+    spec = c1_spec(50, 14)
+    big = max(spec["spheres"][:-1], key=lambda s: s["radius"])
+    c = big["center"]
+    spec = c1_spec(50, 14, (c[0] + 0.1, c[1] - 0.05, c[2] - 0.2))
+    blob = P.pack_scene(scenes.build_scene(spec))
+    S = len(spec["spheres"])
+    at = int(blob[L.H_CAMREL])
+    rel = blob[at:at + S * L.CAMREL_WORDS].reshape(S, L.CAMREL_WORDS)
+    assert sorted(rel[:, 3]) == [0.0] + [1.0] * (S - 1)
+    four_ways(hip, spec, 3)
+
+
+def test_nine_spheres_culled_kernel(hip):
+    """Eight spheres and the ground: the culled kernel, which keeps the per-lane subtraction (its blob
+    carries the table all the same)."""
+    spec = scenes.with_camera(scenes.random_spec(8, 4, 50, 14), position=[0.3, 0.7, -2.1], width=50, height=14)
+    assert len(spec["spheres"]) == 9
+    four_ways(hip, spec, 3, small=False)
+
+
+# ---------------------------------------------------------------------------------------------
+# the sine
+# ---------------------------------------------------------------------------------------------
+
+INV_PI = float.fromhex("0x1.45f306dc9c883p-2")
+PI_PARTS = [float.fromhex(v) for v in ("0x1.921fb54442d18p+1", "0x1.1a62633145c07p-53", "-0x1.f1976b7ed8fbcp-109")]
+COEF = [float.fromhex(v) for v in (
+    "0x1.71b8ef6dcf572p-66", "-0x1.2f49b46814157p-57", "0x1.952c77030ad4ap-49", "-0x1.ae7f3e733b81fp-41",
+    "0x1.6124613a86d09p-33", "-0x1.ae64567f544e4p-26", "0x1.71de3a556c734p-19", "-0x1.a01a01a01a01ap-13",
+    "0x1.1111111111111p-7", "-0x1.5555555555555p-3")]
+
+
+def fma(a, b, c):
+    """a * b + c rounded once (float() of a Fraction rounds to nearest even)."""
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def sin_chain(x):
+    """rtx_device.h's sin_reduced, step by step: every product and fused step rounded exactly once."""
+    n = float(np.rint(np.float64(x) * np.float64(INV_PI)))
+    r = x
+    for p in PI_PARTS:
+        r = fma(-n, p, r)
+    z = float(np.float64(r) * np.float64(r))
+    q = COEF[0]
+    for c in COEF[1:]:
+        q = fma(z, q, c)
+    s = fma(float(np.float64(r) * np.float64(z)), q, r)
+    return -s if int(n) & 1 else s
+
+
+def sine_phases():
+    rng = np.random.default_rng(11)
+    xs = [0.0, 2.0**-30, -(2.0**-30), 2.0**20, -(2.0**20)]
+    for k in (1, 2, 3, 4, 5, 7, 100, 101, 4099, 333333, 667543, -1, -2, -3, -8, -4099, -667544):
+        m = np.float64(k) * np.float64(np.pi / 2)
+        if abs(m) <= 2.0**20:
+            xs += [float(m), float(np.nextafter(m, np.inf)), float(np.nextafter(m, -np.inf))]
+    xs += list(rng.uniform(-(2.0**20), 2.0**20, 256 - len(xs)))
+    assert len(xs) == 256
+    return np.asarray(xs, dtype=np.float64)
+
+
+def test_sine_matches_the_exact_fma_chain(hip):
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+
+    xs = sine_phases()
+    want = np.asarray([sin_chain(float(x)) for x in xs], dtype=np.float64)
+    assert float(np.abs(want - np.sin(xs)).max()) < 1e-15  # the chain is a sine
+    x = torch.from_numpy(xs).cuda()
+    out = torch.full_like(x, float("nan"))
+    L.check(L.load().rtx_selftest_sin(x.data_ptr(), x.numel(), out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+            "rtx_selftest_sin")
+    got = out.cpu().numpy()
+    bad = np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
+    assert bad.size == 0, [(float(xs[i]).hex(), float(got[i]).hex(), float(want[i]).hex()) for i in bad[:5]]
