@@ -34,7 +34,6 @@ __global__ __launch_bounds__(kBlock) void k_primary_aovs(Params p, AovOut o) {
   const cdouble* sc = (const cdouble*)p.scene;
   // a blob that is not a packed scene of p.nsph spheres is traced as an empty scene: every ray misses
   const int nsph = (sc[RTX_H_MAGIC] == RTX_MAGIC && sc[RTX_H_NSPH] == (double)p.nsph) ? p.nsph : 0;
-  const cdouble* geo = sc + RTX_HDR_WORDS;
   const double* tab = p.scene + RTX_HDR_WORDS;
   const double nan = __builtin_nan("");  // the reference expressions in every sphere test (SphTest)
   bool lit = false;
@@ -45,15 +44,8 @@ __global__ __launch_bounds__(kBlock) void k_primary_aovs(Params p, AovOut o) {
     // base.py:97-103: the nearest distance, how many shapes share it, the first of them in scene order
     double tmin = FARAWAY;
     int nh = 0, first = nsph;
-    if (nsph > 0 && sc[RTX_H_NNODES] != 0.0) {
-      nearest_count_bvh(sc, ox, oy, oz, oo, dx, dy, dz, tmin, nh, first);
-    } else {  // no culling tree (fewer than kTreeMinSpheres spheres): the table in scene order
-      for (int s = 0; s < nsph; ++s) {
-        const cdouble* g = geo + __builtin_amdgcn_readfirstlane(s) * RTX_GEOM_WORDS;
-        isect_one(isect_disc(g, ox, oy, oz, oo, dx, dy, dz, nan),
-                  [&](double t, bool v) { count_update(v, t, s, tmin, nh, first); });
-      }
-    }
+    // (without a culling tree, fewer than kTreeMinSpheres spheres: the table in scene order)
+    nearest_count(sc, nsph, nsph > 0 && sc[RTX_H_NNODES] != 0.0, ox, oy, oz, oo, dx, dy, dz, tmin, nh, first);
     const bool hit = nh > 0 && tmin != FARAWAY;  // (nearest != FARAWAY) & (distance == nearest), base.py:102-103
     if (o.depth) __builtin_nontemporal_store(tmin, o.depth + i);
     if (o.id) __builtin_nontemporal_store(hit ? first : -1, o.id + i);
@@ -92,24 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_primary_aovs(Params p, AovOut o) {
         const int h0 = __builtin_amdgcn_readfirstlane(h);
         const int hs = __ballot(h != h0) == 0 ? h0 : nsph;
         const double tself = isect_t(gh, qx, qy, qz, qq, lx, ly, lz, nan);
-        // t_self beyond FARAWAY: every missing sphere shadows; the tree skips missing spheres, so
-        // such a wave takes the linear loop
-        const bool far_self = tself > FARAWAY;
-        lit = true;
-        if (sc[RTX_H_NNODES] != 0.0 && __ballot(far_self) == 0) {
-          Work<false> wk;
-          lit = lit_bvh(sc, qx, qy, qz, qq, lx, ly, lz, tself, hs, nan, wk);
-        } else {
-          for (int j = 0; j < nsph; ++j) {
-            if (j == hs) continue;
-            const cdouble* g = geo + __builtin_amdgcn_readfirstlane(j) * RTX_GEOM_WORDS;
-            bool sh = far_self;  // lanes without a valid root
-            isect_one(isect_disc(g, qx, qy, qz, qq, lx, ly, lz, nan),
-                      [&](double t, bool v) { sh = shadows(v, t, tself, far_self); });
-            if (sh) lit = false;
-            if (__ballot(lit) == 0) break;  // every lane of the wave is in shadow
-          }
-        }
+        lit = nothing_nearer(sc, nsph, qx, qy, qz, qq, lx, ly, lz, tself, hs);
       }
     }
     const int64_t n = p.n;

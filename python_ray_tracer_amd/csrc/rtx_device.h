@@ -91,34 +91,25 @@ constexpr int kFwdWavesSmall = 5;    // ... and of the TREE = false kernels (TP 
 constexpr int kDeepLevels = 5;       // fast-kernel levels before a longer chain is deferred (A/B: 3, 5, 8; the
                                      // 8-level instantiation spills, 3 defers too many pixels)
 constexpr int kCappedMax = RTX_FAST_MAX_BOUNCES;  // caps rendered entirely by k_render_fast<cap>
-// shading-only terms (the view vector, the half vector and the specular's internal divisions and
-// square roots; none of them decides a hit, a shadow, a checker cell or a reflected ray):
-//   0 = the wave-uniform range-checked correctly rounded paths;
-//   1 = the correctly rounded cores without range checks (operands in range by construction);
-//   3 = the specular's divisions and square roots by shorter Newton sequences (within ~1 ulp,
-//       tools/approx_probe), V and H normalised by the correctly rounded cores (A/B on identical
-//       parity: C2 -6.4%, C2main -8.5%, C5 -2.9%, C3 -2.8% against 1);
-//   2 / 4 = also V and H (2) or H (4) by rsq + Newton: N.V near grazing amplifies their rounding,
-//       C4 and 1080p colour moved by 1.4e-12 (over the 1e-12 bar), not adopted.
-constexpr int kShadeMath = 3;
-// The small-scene wave (small_wave, TP 0), each switch an A/B of its own (profiles/optimistic_C2_ab.json):
-// the optimistic first body of the counter-free capped builds, one guard verdict per wave instead of
-// a ballot and a branch per helper; false: the guarded body alone
-constexpr bool kSmallOptimistic = true;
-// the sphere table requested with the header words and held in registers until the level-0 search
-// has found a hit (an all-sky wave never waits for it); false: staged in LDS before the tile
-constexpr bool kSmallLateStage = true;
-// Wave-uniform terms kept out of the vector unit, each switch an A/B of its own on identical frames
-// (profiles/uniform_terms_C2.json):
+// Shading-only terms (the view vector, the half vector and the specular's internal divisions and
+// square roots; none of them decides a hit, a shadow, a checker cell or a reflected ray): the
+// specular's divisions and square roots take shorter Newton sequences (within ~1 ulp,
+// tools/approx_probe), V and H are normalised by the correctly rounded cores (div_shade, sqrt_shade,
+// inv_mag_shade; A/B on identical parity against the correctly rounded cores throughout: C2 -6.4%,
+// C2main -8.5%, C5 -2.9%, C3 -2.8%).
+// The small-scene wave (small_wave, TP 0; profiles/optimistic_C2_ab.json, C2 50.05 -> 47.81 us with
+// both): the counter-free capped builds run an optimistic first body, one guard verdict per wave
+// instead of a ballot and a branch per helper (alone -3.4%); and the sphere table is requested with
+// the header words and held in registers until the level-0 search has found a hit, so an all-sky wave
+// never waits for it (alone -3.1%).
+// Wave-uniform terms kept out of the vector unit (profiles/uniform_terms_C2.json, identical frames):
 // the level-0 search of the small-scene kernels takes camera - centre and the sign of the camera's c
-// from the packer's table (RTX_H_CAMREL) instead of three subtractions of scalars per sphere and lane
-constexpr bool kCamRelTable = true;
-// the small-scene kernels' camera ray: a wave whose tile ends before the frame's last column and row
-// (a scalar decision from the tile's position) computes the linspace points without the stop-word
-// selects; the fix words of the others are tested by their bits (f64_nonzero_bits: a scalar test where
-// the compare of doubles is a vector instruction; same verdict for every double). It relies on one
-// wave tile per block (a static_assert in fast_tile_body): set it false to tune kFastWavesSmall
-constexpr bool kCameraStraight = true;
+// from the packer's table (RTX_H_CAMREL) instead of three subtractions of scalars per sphere and lane;
+// and in their camera ray a wave whose tile ends before the frame's last column and row (a scalar
+// decision from the tile's position) computes the linspace points without the stop-word selects, the
+// fix words of the others being tested by their bits (f64_nonzero_bits: a scalar test where the
+// compare of doubles is a vector instruction; same verdict for every double). The latter relies on one
+// wave tile per block (a static_assert in fast_tile_body ties it to kFastWavesSmall = 1).
 // (Built, measured and taken out again, profiles/uniform_terms_C2.json: the sine's polynomial with its
 // coefficients as scalar operands of v_fma_f64, and the header's counts read as bit patterns. Neither
 // moved C2's time, and with both the culled kernels, which share shade, lost 0.3-0.6%.)
@@ -814,6 +805,22 @@ __device__ __forceinline__ void nearest_count_bvh(const cdouble* sc, double ox, 
         return true;
       });
 }
+// The same of the pass kernels (aov, glass): through the tree when `tree` (wave-uniform) says so, else
+// the table in scene order. tmin, nh and first come in as FARAWAY, 0 and nsph.
+__device__ __forceinline__ void nearest_count(const cdouble* sc, int nsph, bool tree, double ox, double oy, double oz,
+                                              double oo, double dx, double dy, double dz, double& tmin, int& nh,
+                                              int& first) {
+  if (tree) {
+    nearest_count_bvh(sc, ox, oy, oz, oo, dx, dy, dz, tmin, nh, first);
+  } else {
+    const cdouble* geo = sc + RTX_HDR_WORDS;
+    for (int s = 0; s < nsph; ++s) {
+      const cdouble* g = geo + __builtin_amdgcn_readfirstlane(s) * RTX_GEOM_WORDS;
+      isect_one(isect_disc(g, ox, oy, oz, oo, dx, dy, dz, __builtin_nan("")),
+                [&](double t, bool v) { count_update(v, t, s, tmin, nh, first); });
+    }
+  }
+}
 
 // Shadow any-hit through the culling tree (shader.py:126-128 in its any-hit form): lit stays true
 // unless some sphere is strictly nearer than the shape itself along the light direction. hs: the
@@ -873,6 +880,33 @@ __device__ __forceinline__ bool lit_bvh(const cdouble* sc, double qx, double qy,
   return lit;
 }
 
+// Any-hit of the ray (q, d) from a hit (the pass kernels: aov's shadow mask, occlusion): true unless
+// some shape is strictly nearer than tself. hs: a shape whose own test is skipped (nsph: none).
+// Through the culling tree where the scene has one and no lane's tself lies beyond FARAWAY (the tree
+// skips missing spheres, which shadow such a lane), else the table in scene order; the two agree.
+__device__ __forceinline__ bool nothing_nearer(const cdouble* sc, int nsph, double qx, double qy, double qz, double qq,
+                                               double dx, double dy, double dz, double tself, int hs) {
+  const cdouble* geo = sc + RTX_HDR_WORDS;
+  const double nan = __builtin_nan("");  // the reference expressions in every sphere test (SphTest)
+  const bool far_self = tself > FARAWAY;
+  bool open = true;
+  if (sc[RTX_H_NNODES] != 0.0 && __ballot(far_self) == 0) {
+    Work<false> wk;
+    open = lit_bvh(sc, qx, qy, qz, qq, dx, dy, dz, tself, hs, nan, wk);
+  } else {
+    for (int s = 0; s < nsph; ++s) {
+      if (s == hs) continue;
+      const cdouble* g = geo + __builtin_amdgcn_readfirstlane(s) * RTX_GEOM_WORDS;
+      bool sh = far_self;  // lanes without a valid root
+      isect_one(isect_disc(g, qx, qy, qz, qq, dx, dy, dz, nan),
+                [&](double t, bool v) { sh = shadows(v, t, tself, far_self); });
+      if (sh) open = false;
+      if (__ballot(open) == 0) break;  // every lane of the wave is decided
+    }
+  }
+  return open;
+}
+
 // Nearest hit of ray (O, D) over all spheres, geometry through
 // the scalar cache. CAM: O is the camera (level 0), using the host-precomputed c.
 template <bool CAM, typename P, typename Wk, typename Tm>
@@ -901,7 +935,7 @@ constexpr int kCamRelAt = RTX_H_CAMREL + 1;
 constexpr int kCamRelHeaderSpheres = (RTX_HDR_WORDS - kCamRelAt) / RTX_CAMREL_WORDS;
 template <int NSPH>
 __device__ __forceinline__ const cdouble* camrel_table(const cdouble* sc, int nsph) {
-  if constexpr (!kCamRelTable || NSPH > kCamRelHeaderSpheres) return nullptr;
+  if constexpr (NSPH > kCamRelHeaderSpheres) return nullptr;
   if (NSPH == 0 && nsph > kCamRelHeaderSpheres) return nullptr;
   return f64_bits(sc[RTX_H_CAMREL]) == f64_bits((double)kCamRelAt) ? sc + kCamRelAt : nullptr;
 }
@@ -958,7 +992,7 @@ __device__ __forceinline__ double sin_ref(const cdouble* sc, double x, Tm tame =
   return sin(x);
 }
 
-// Shading-only arithmetic (kShadeMath): operands are non-negative and far from the overflow range
+// Shading-only arithmetic: operands are non-negative and far from the overflow range
 // by construction (denominators >= 1e-8, square-root arguments in [0, 2], |V|^2 and |H|^2 the
 // squared lengths of finite vectors; a zero argument is selected around the core). The cores are
 // bit-identical to the range-checked paths for operands above ~2^-900; below, only terms that are
@@ -966,8 +1000,6 @@ __device__ __forceinline__ double sin_ref(const cdouble* sc, double x, Tm tame =
 // rcp: the hardware estimate (~2^-24) and two Newton steps, correctly rounded on 4 M random
 // operands (tools/approx_probe); a * rcp(b) is then within ~1 ulp of a / b.
 __device__ __forceinline__ double div_shade(double a, double b) {
-  if constexpr (kShadeMath == 0) return div_cr(a, b);
-  if constexpr (kShadeMath == 1) return div_core(a, b);  // (2, 3, 4: the Newton sequence below)
   double r = __builtin_amdgcn_rcp(b);
   r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
   r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
@@ -976,8 +1008,6 @@ __device__ __forceinline__ double div_shade(double a, double b) {
 // sqrt: the library core without its second correction (correctly rounded on the same sample);
 // 0 stays 0 (rsq(0) = inf)
 __device__ __forceinline__ double sqrt_shade(double x) {
-  if constexpr (kShadeMath == 0) return sqrt_cr(x);
-  if constexpr (kShadeMath == 1) return x == 0.0 ? 0.0 : sqrt_core(x);
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = y * 0.5;
   const double r = __builtin_fma(-h, g, 0.5);
@@ -987,21 +1017,12 @@ __device__ __forceinline__ double sqrt_shade(double x) {
   g = __builtin_fma(d, h, g);
   return x == 0.0 ? 0.0 : g;
 }
-// 1 / where(|v| == 0, 1, |v|) for d = |v|^2: rsq and two Newton steps (~1 ulp)
+// 1 / where(|v| == 0, 1, |v|) for d = |v|^2, the normalisation of the view vector V and the half
+// vector H, by the correctly rounded cores. Not by rsq and Newton steps (~1 ulp) like the two above:
+// N.V near grazing amplifies the shorter sequence's rounding (4 N.V + 1e-8 and G1(N.V) divide by it),
+// and C4 and 1080p colour moved by 1.4e-12, over the 1e-12 parity bar, with V and H or H alone so.
 __device__ __forceinline__ double inv_mag_shade(double d) {
-  if constexpr (kShadeMath == 0) return inv_mag(d);
-  if constexpr (kShadeMath == 1 || kShadeMath == 3) return d == 0.0 ? 1.0 : div_core(1.0, sqrt_core(d));
-  double y = __builtin_amdgcn_rsq(d);
-  y = __builtin_fma(y * 0.5, __builtin_fma(-d * y, y, 1.0), y);
-  y = __builtin_fma(y * 0.5, __builtin_fma(-d * y, y, 1.0), y);
-  return d == 0.0 ? 1.0 : y;
-}
-
-// the view vector: N.V near grazing amplifies its rounding (4 N.V + 1e-8 and G1(N.V) divide by
-// it), so variants 3 and 4 keep its normalisation correctly rounded
-__device__ __forceinline__ double inv_mag_shade_v(double d) {
-  if constexpr (kShadeMath == 3 || kShadeMath == 4) return d == 0.0 ? 1.0 : div_core(1.0, sqrt_core(d));
-  return inv_mag_shade(d);
+  return d == 0.0 ? 1.0 : div_core(1.0, sqrt_core(d));
 }
 
 __device__ __forceinline__ double pow5(double x) {
@@ -1067,7 +1088,7 @@ __device__ __forceinline__ double specular(const M* mh, double g, double nx, dou
   double Hx = Lx + Vx, Hy = Ly + Vy, Hz = Lz + Vz;
   {  // :280
     const double dh = dot3(Hx, Hy, Hz, Hx, Hy, Hz);
-    const double rh = kShadeMath == 4 ? inv_mag_shade(dh) : inv_mag_shade_v(dh);
+    const double rh = inv_mag_shade(dh);
     Hx = Hx * rh;
     Hy = Hy * rh;
     Hz = Hz * rh;
@@ -1373,7 +1394,7 @@ __device__ __forceinline__ void shade(const cdouble* sc, const G* geo, const T* 
   if (weighted || need_irid) {
     double vx = sc[RTX_H_CAM + 0] - px, vy = sc[RTX_H_CAM + 1] - py, vz = sc[RTX_H_CAM + 2] - pz;
     {  // :76 (towards the camera on every level); V only feeds the specular and the iridescence
-      const double rv = inv_mag_shade_v(dot3(vx, vy, vz, vx, vy, vz));
+      const double rv = inv_mag_shade(dot3(vx, vy, vz, vx, vy, vz));
       vx = vx * rv;
       vy = vy * rv;
       vz = vz * rv;
@@ -1437,7 +1458,7 @@ __device__ __forceinline__ void camera_dir(const cdouble* sc, int col, int r, in
   dy = vy * rr;
   dz = vz * rr;
 }
-// camera_dir of the small-scene kernels (kCameraStraight; a function of its own, so that every other
+// camera_dir of the small-scene kernels (a function of its own, so that every other
 // caller compiles from unchanged text). inner (wave-uniform): no lane of the wave is in the frame's
 // last column or row, so the linspace stops are not even asked about; the other waves take the selects
 // above with the fix words read by their bits.
@@ -1590,10 +1611,10 @@ __device__ __forceinline__ void nearest_masked(const P* geo, uint64_t m0, uint64
 // than 2^6 or the candidates more than kBeamMaxCand.
 constexpr int kBeamPasses = 3;
 constexpr int kBeamMaxCand = 24;
-// The beam kernels stage, in the LDS copy of the sphere table, each sphere's own part of the test's
-// radius in geometry word RTX_G_IDX (unused in the main table): r (bounded above) plus the margin's
-// per-sphere terms, beam_word below. The per-lane test then needs no square root of its own.
-constexpr bool kBeamStaged = true;
+// The beam kernels with an LDS copy of the sphere table stage in it each sphere's own part of the
+// test's radius, in geometry word RTX_G_IDX (unused in the main table): r (bounded above) plus the
+// margin's per-sphere terms, beam_word below. The per-lane test then needs no square root of its own.
+// (Without the copy, LDS = false: more than kLdsMaxSpheres spheres, the test computes that part itself.)
 static_assert(RTX_GEOM_WORDS == 8 && RTX_G_IDX == 7, "beam word: the last geometry word");
 struct Beam {
   uint64_t m[kBeamPasses];  // pass j: candidate bits at the testing lanes' positions
@@ -1920,7 +1941,7 @@ __device__ __forceinline__ bool fast_tile_body(const Params& p, int bx, int by, 
       ox = rin[0]; oy = rin[1]; oz = rin[2];
       dx = rin[3]; dy = rin[4]; dz = rin[5];
     } else if (cam0) {
-      if constexpr (kCameraStraight && !TREE) {
+      if constexpr (!TREE) {
         // a whole-frame launch's tile that ends before the frame's last column and row (so it is not
         // clipped either): the straight-line camera ray. Row tiles (n_parts > 1) keep the selects.
         static_assert(WX == 1 && WY == 1, "one wave tile per block: (bx, by) is the wave's tile");
@@ -2080,7 +2101,7 @@ __device__ __forceinline__ bool fast_tile_body(const Params& p, int bx, int by, 
       // the wave's beam candidates (tame scenes up to 128 spheres), else the culling tree
       Beam bm;
       const double* btab = LDS ? (const double*)lds_tab : p.scene + RTX_HDR_WORDS;
-      if (BEAM && sc[RTX_H_TAME] != 0.0 && wave_beam<kBeamStaged && LDS>(btab, nb, ox, oy, oz, dx, dy, dz, bm)) {
+      if (BEAM && sc[RTX_H_TAME] != 0.0 && wave_beam<LDS>(btab, nb, ox, oy, oz, dx, dy, dz, bm)) {
         if (st) stat_wave(st, RTX_S_BEAMW);
         for (int j = 0; j < bm.passes; ++j) wk.beam();  // a lane's cone test of one sphere per pass
         nearest_beam(geo, nsph, bm, ox, oy, oz, dx, dy, dz, tmin, hit, tie, tame, wk);
@@ -2186,7 +2207,7 @@ k_render_fast(Params p0) {
     const double* src = p.scene + RTX_HDR_WORDS;
     for (int k = threadIdx.x; k < p.nsph * kSphWords; k += fast_block<TREE>()) {
       // (the beam kernels: geometry word RTX_G_IDX of the copy holds beam_word, see wave_beam)
-      const bool bw = BEAM && kBeamStaged && k < p.nsph * RTX_GEOM_WORDS && (k & (RTX_GEOM_WORDS - 1)) == RTX_G_IDX;
+      const bool bw = BEAM && k < p.nsph * RTX_GEOM_WORDS && (k & (RTX_GEOM_WORDS - 1)) == RTX_G_IDX;
       lds_tab[k] = bw ? beam_word(src[k - RTX_G_IDX + RTX_G_CC], src[k - RTX_G_IDX + RTX_G_RR]) : src[k];
     }
   }
@@ -2307,10 +2328,8 @@ __device__ __forceinline__ void small_wave(const Params& p, double* lds_tab) {
   const int nw0 = p.nsph * kSphWords;
   const int lane = threadIdx.x;
   double tv[NL];
-  if constexpr (kSmallLateStage) {
 #pragma unroll
-    for (int j = 0; j < NL; ++j) tv[j] = lane + 64 * j < nw0 ? src[lane + 64 * j] : 0.0;
-  }
+  for (int j = 0; j < NL; ++j) tv[j] = lane + 64 * j < nw0 ? src[lane + 64 * j] : 0.0;
   // One tile per block. Bottom tile rows are dispatched first: they hold the ground and the
   // spheres, whose pixels run long bounce chains, while sky rows finish at level 0 and so fill the
   // end of the grid (longest-first order; A/B: C2 -10%). Output does not depend on the order. Blocks
@@ -2318,7 +2337,7 @@ __device__ __forceinline__ void small_wave(const Params& p, double* lds_tab) {
   // dispatch slot b to block tile order[b], block tile t being (t % gridDim.x, bottom-up row
   // t / gridDim.x), and a cost record takes each block's time.
   uint32_t tb = blockIdx.y * gridDim.x + blockIdx.x;
-  if constexpr (kSmallLateStage) {  // (the kernarg fields the tile needs further down, in the batch of the ones needed here)
+  {  // (the kernarg fields the tile needs further down, in the batch of the ones needed here)
     const uint32_t gy = gridDim.y;
     asm volatile("" ::"s"(p.tile_div), "s"(gy), "s"(p.n), "s"(p.part_run), "s"(p.out), "s"(p.no_general));
   }
@@ -2328,18 +2347,15 @@ __device__ __forceinline__ void small_wave(const Params& p, double* lds_tab) {
   // requested together and waited for once, here, with the table loads in flight. (The linspace stop
   // words are left to camera_dir, whose last column and row alone read them: with them here the
   // NSPH 3, B 3 build spills.)
-  if constexpr (kSmallLateStage) {
+  {
     const double htame = sc[RTX_H_TAME], c0 = sc[RTX_H_CAM + 0], c1 = sc[RTX_H_CAM + 1], c2 = sc[RTX_H_CAM + 2];
     const double x0 = sc[RTX_H_XSTART], x1 = sc[RTX_H_XSTEP], y0 = sc[RTX_H_YSTART], y1 = sc[RTX_H_YSTEP];
     const double xf = sc[RTX_H_XFIX], yf = sc[RTX_H_YFIX];
     const double vz = sc[RTX_H_VZ], vz2 = sc[RTX_H_VZ2];
-    if constexpr (NSPH >= 1 && NSPH <= 3 && kCamRelTable) {  // (... and the word that says whether the table is there)
+    if constexpr (NSPH >= 1 && NSPH <= 3) {  // (... and the word that says whether the table is there)
       const double crel = sc[RTX_H_CAMREL];
       asm volatile("" ::"s"(magic), "s"(hn), "s"(htame), "s"(tb), "s"(c0), "s"(c1), "s"(c2), "s"(x0), "s"(x1), "s"(y0),
                    "s"(y1), "s"(xf), "s"(yf), "s"(vz), "s"(vz2), "s"(crel));
-    } else if constexpr (NSPH >= 1 && NSPH <= 3) {
-      asm volatile("" ::"s"(magic), "s"(hn), "s"(htame), "s"(tb), "s"(c0), "s"(c1), "s"(c2), "s"(x0), "s"(x1), "s"(y0),
-                   "s"(y1), "s"(xf), "s"(yf), "s"(vz), "s"(vz2));
     } else {  // (more spheres, or a run-time count: with the camera words held from here these builds spill)
       asm volatile("" ::"s"(magic), "s"(hn), "s"(htame), "s"(tb));
     }
@@ -2364,13 +2380,7 @@ __device__ __forceinline__ void small_wave(const Params& p, double* lds_tab) {
     by = (int)(gridDim.y - 1 - q);
   }
   bool staged = false;  // wave-uniform: the LDS table is complete
-  if constexpr (!kSmallLateStage) {
-    for (int k = lane; k < nw; k += 64) lds_tab[k] = src[k];
-    __syncthreads();
-    staged = true;
-  }
   auto stage_regs = [&](int hit) {
-    if constexpr (!kSmallLateStage) return;
     if (nw > 64 * NL) {  // (a run-time count beyond the small scenes': straight from memory)
       for (int k = lane; k < nw; k += 64) lds_tab[k] = src[k];
       __syncthreads();
@@ -2385,7 +2395,7 @@ __device__ __forceinline__ void small_wave(const Params& p, double* lds_tab) {
   };
   // (NSPH > 0: every scene below kTreeMinSpheres has a build of its own count, go_ns; the run-time-count
   // build serves none of them and would spill with two bodies)
-  constexpr bool OPT = kSmallOptimistic && DEEP == 0 && !STATS && !IMG && NSPH > 0;
+  constexpr bool OPT = DEEP == 0 && !STATS && !IMG && NSPH > 0;
   bool redo = true;
   if constexpr (OPT) {
     if (p.mode == 0 && sc[RTX_H_TAME] != 0.0) {

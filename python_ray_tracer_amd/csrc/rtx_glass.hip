@@ -22,10 +22,9 @@ constexpr int64_t kGlassMaxWorkers = 196608;
 // waves per SIMD the kernel is compiled for (A/B against 4, which takes 127 VGPRs and spills 4, with 262,144
 // workers: B = 3 -2.8%, B = 5 +2.9%)
 constexpr int kGlassWaves = 3;
-// The stacks in LDS instead ([entry][word][lane], 4 KB per entry and wave), an A/B switch (tools/ab_build.py
-// --set): caps up to 3 only (16 entries are the 64 KB a block may ask for), two waves per CU. Measured
-// 2.7x slower at B = 3 (profiles/glass_ab.json): the product keeps the stacks in the workspace.
-constexpr bool kGlassLdsStack = false;
+// (The stacks are in the workspace, not in LDS: [entry][word][lane] there is 4 KB per entry and wave, so the
+// 64 KB a block may ask for hold caps up to 3 only and two waves per CU, measured 2.7x slower at B = 3;
+// DESIGN.md §14, profiles/glass_ab.json.)
 
 __host__ __device__ constexpr int glass_stack_entries(int B) { return 4 * B + 4; }
 
@@ -60,12 +59,7 @@ struct RayStack {
   int64_t nw;
   int64_t w;
   __device__ __forceinline__ double& at(int e, int f) const {
-    if constexpr (kGlassLdsStack) {
-      extern __shared__ double lds_stack[];
-      return lds_stack[(e * kRayWords + f) * 64 + threadIdx.x];
-    } else {
-      return base[((int64_t)e * kRayWords + f) * nw + w];
-    }
+    return base[((int64_t)e * kRayWords + f) * nw + w];
   }
   __device__ __forceinline__ void push(int e, double ox, double oy, double oz, double dx, double dy, double dz,
                                        double wt, int level) const {
@@ -156,15 +150,7 @@ void k_trace_glass(GlassParams p) {
         // the nearest distance (base.py:97-98), how many shapes share it and the first in scene order
         tmin = FARAWAY;
         int nh = 0, first = nsph;
-        if (tree) {
-          nearest_count_bvh(sc, ox, oy, oz, oo, dx, dy, dz, tmin, nh, first);
-        } else {
-          for (int s = 0; s < nsph; ++s) {
-            const cdouble* g = geo + __builtin_amdgcn_readfirstlane(s) * RTX_GEOM_WORDS;
-            isect_one(isect_disc(g, ox, oy, oz, oo, dx, dy, dz, nan),
-                      [&](double t, bool v) { count_update(v, t, s, tmin, nh, first); });
-          }
-        }
+        nearest_count(sc, nsph, tree, ox, oy, oz, oo, dx, dy, dz, tmin, nh, first);
         left = tmin != FARAWAY ? nh : 0;  // (nearest != FARAWAY) & (t == nearest), base.py:102-103
         if (left == 0) continue;
         h = first;
@@ -269,8 +255,6 @@ extern "C" int rtx_trace_glass(const double* scene, int n_spheres, const double*
   p.status = (uint32_t*)workspace + RTX_WS_STATUS;
   p.stack = (double*)((uint8_t*)workspace + RTX_WS_HDR_BYTES);
   p.n_workers = glass_workers(n, max_bounces);
-  const size_t lds = kGlassLdsStack ? (size_t)glass_stack_entries(max_bounces) * kRayWords * 64 * 8 : 0;
-  if (lds > 65536) return rtx_fail(RTX_E_ARG, "the LDS-stack build traces caps up to 3, got %d", max_bounces);
-  hipLaunchKernelGGL(k_trace_glass, dim3((unsigned)(p.n_workers / 64)), dim3(64), (unsigned)lds, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(k_trace_glass, dim3((unsigned)(p.n_workers / 64)), dim3(64), 0, (hipStream_t)stream, p);
   return rtx_launched("k_trace_glass");
 }

@@ -299,9 +299,9 @@ __global__ __launch_bounds__(kBlock) void k_quantize(const T* __restrict__ c, in
 // K == 0: k at run time.
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 constexpr int kResolveBlocksPerCu = 8;  // grid cap of k_resolve (blocks per CU), grid-strided beyond it
-// one thread per output pixel and channel plane of the colour outputs, instead of per pixel with its
-// three planes (u8 always takes the pixel: its three bytes are neighbours)
-constexpr bool kResolvePerPlane = false;
+// One thread per output pixel with its three planes, for every output kind: the u8 output needs a pixel's
+// three channels in one lane (its bytes are neighbours), and the mapping already runs at 4.9-5.9 TB/s,
+// above a plain streaming read of the sample frame (3.7 TB/s).
 
 template <int K, bool VEC>
 __device__ __forceinline__ double resolve_block(const double* __restrict__ s, int64_t row_stride, int k) {
@@ -329,7 +329,7 @@ __device__ __forceinline__ double resolve_block(const double* __restrict__ s, in
 // samples: n_frames x [3][k*n_rows][k*width]; out: n_frames x (width * n_rows pixels as out_kind
 // says). k*k*width*n_rows*n_frames < 2^31 (checked by the host), so pixel indices fit 32 bits; the
 // word offsets (three planes) are 64-bit.
-template <int K, bool VEC, bool PLANE>
+template <int K, bool VEC>
 __global__ __launch_bounds__(kBlock) void k_resolve(const double* __restrict__ samples, int k, unsigned width,
                                                     unsigned n_rows, unsigned n_frames, void* __restrict__ out,
                                                     int out_kind) {
@@ -337,23 +337,12 @@ __global__ __launch_bounds__(kBlock) void k_resolve(const double* __restrict__ s
   const unsigned n = width * n_rows;                // pixels of a frame
   const int64_t row_stride = (int64_t)kk * width;   // samples of a sample row
   const int64_t ns = row_stride * kk * n_rows;      // samples of a plane
-  const int64_t items = (int64_t)n * n_frames * (PLANE ? 3 : 1);
+  const int64_t items = (int64_t)n * n_frames;
   for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < items; t += (int64_t)gridDim.x * kBlock) {
-    const unsigned px = PLANE ? (unsigned)(t / 3) : (unsigned)t;  // frame-major pixel index
+    const unsigned px = (unsigned)t;  // frame-major pixel index
     const unsigned f = px / n, i = px - f * n;
     const unsigned r = i / width, c = i - r * width;
     const double* s = samples + (int64_t)f * 3 * ns + (int64_t)r * kk * row_stride + (int64_t)c * kk;
-    if (PLANE) {  // colour outputs only
-      const unsigned ch = (unsigned)(t - (int64_t)px * 3);
-      const double v = resolve_block<K, VEC>(s + ch * ns, row_stride, k);
-      const int64_t o = ((int64_t)f * 3 + ch) * n + i;
-      if (out_kind == RTX_OUT_F32_SOA) {
-        __builtin_nontemporal_store((float)v, (float*)out + o);
-      } else {
-        __builtin_nontemporal_store(v, (double*)out + o);
-      }
-      continue;
-    }
     const double cr = resolve_block<K, VEC>(s, row_stride, k);
     const double cg = resolve_block<K, VEC>(s + ns, row_stride, k);
     const double cb = resolve_block<K, VEC>(s + 2 * ns, row_stride, k);
@@ -1007,37 +996,27 @@ int rtx_resolve_samples(const double* samples, int k, int width, int n_rows, int
   const bool fits = width <= room && n_rows <= (room /= width) && n_frames <= (room /= n_rows);
   if (!fits) return rtx_fail(RTX_E_ARG, "k*k*width*n_rows*n_frames must stay below 2^31 samples per plane");
   const bool vec = k % 2 == 0 && (uintptr_t)samples % 16 == 0;
-  const bool plane = kResolvePerPlane && out_kind != RTX_OUT_U8_HWC;
-  const int64_t items = (int64_t)width * n_rows * n_frames * (plane ? 3 : 1);
+  const int64_t items = (int64_t)width * n_rows * n_frames;
   const int64_t cap = (int64_t)device_cus() * kResolveBlocksPerCu, want = (items + kBlock - 1) / kBlock;
   const dim3 grid((unsigned)(want < cap ? want : cap));
-#define RTX_RESOLVE(K, VEC, PLANE)                                                                             \
-  hipLaunchKernelGGL((k_resolve<K, VEC, PLANE>), grid, dim3(kBlock), 0, (hipStream_t)stream, samples, k,       \
+#define RTX_RESOLVE(K, VEC)                                                                              \
+  hipLaunchKernelGGL((k_resolve<K, VEC>), grid, dim3(kBlock), 0, (hipStream_t)stream, samples, k,        \
                      (unsigned)width, (unsigned)n_rows, (unsigned)n_frames, out, out_kind)
-#define RTX_RESOLVE_K(K, VEC)      \
-  do {                             \
-    if (plane) {                   \
-      RTX_RESOLVE(K, VEC, true);   \
-    } else {                       \
-      RTX_RESOLVE(K, VEC, false);  \
-    }                              \
-  } while (0)
   if (k == 2 && vec) {
-    RTX_RESOLVE_K(2, true);
+    RTX_RESOLVE(2, true);
   } else if (k == 2) {
-    RTX_RESOLVE_K(2, false);
+    RTX_RESOLVE(2, false);
   } else if (k == 3) {
-    RTX_RESOLVE_K(3, false);
+    RTX_RESOLVE(3, false);
   } else if (k == 4 && vec) {
-    RTX_RESOLVE_K(4, true);
+    RTX_RESOLVE(4, true);
   } else if (k == 4) {
-    RTX_RESOLVE_K(4, false);
+    RTX_RESOLVE(4, false);
   } else if (vec) {
-    RTX_RESOLVE_K(0, true);
+    RTX_RESOLVE(0, true);
   } else {
-    RTX_RESOLVE_K(0, false);
+    RTX_RESOLVE(0, false);
   }
-#undef RTX_RESOLVE_K
 #undef RTX_RESOLVE
   return check_launch("k_resolve");
 }

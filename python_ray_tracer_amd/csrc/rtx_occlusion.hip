@@ -61,33 +61,6 @@ __device__ __forceinline__ Frame frame_around(double nx, double ny, double nz) {
   return f;
 }
 
-// Any-hit of the ray (q, d) from a hit: true unless some shape is strictly nearer than tself. hs: a
-// shape whose own test is skipped (nsph: none). Through the culling tree where the scene has one and
-// no lane's tself lies beyond FARAWAY (the tree skips missing spheres, which shadow such a lane),
-// else the table in scene order; the two agree.
-__device__ __forceinline__ bool nothing_nearer(const cdouble* sc, int nsph, double qx, double qy, double qz, double qq,
-                                               double dx, double dy, double dz, double tself, int hs) {
-  const cdouble* geo = sc + RTX_HDR_WORDS;
-  const double nan = __builtin_nan("");  // the reference expressions in every sphere test (SphTest)
-  const bool far_self = tself > FARAWAY;
-  bool open = true;
-  if (sc[RTX_H_NNODES] != 0.0 && __ballot(far_self) == 0) {
-    Work<false> wk;
-    open = lit_bvh(sc, qx, qy, qz, qq, dx, dy, dz, tself, hs, nan, wk);
-  } else {
-    for (int s = 0; s < nsph; ++s) {
-      if (s == hs) continue;
-      const cdouble* g = geo + __builtin_amdgcn_readfirstlane(s) * RTX_GEOM_WORDS;
-      bool sh = far_self;  // lanes without a valid root
-      isect_one(isect_disc(g, qx, qy, qz, qq, dx, dy, dz, nan),
-                [&](double t, bool v) { sh = shadows(v, t, tself, far_self); });
-      if (sh) open = false;
-      if (__ballot(open) == 0) break;  // every lane of the wave is decided
-    }
-  }
-  return open;
-}
-
 // One lane per ray, ray i = blockIdx.x * kBlock + threadIdx.x: the 64 lanes of a wave hold 64
 // consecutive rays, so its id / position / normal loads and its float stores are contiguous runs.
 // The sample loop is wave-uniform (the table row through the scalar cache); only the rotation is a

@@ -1,4 +1,4 @@
-"""Wave-uniform terms kept out of the vector unit (rtx_device.h: kCamRelTable, kCameraStraight) change
+"""Wave-uniform terms kept out of the vector unit (rtx_device.h: camrel_table, camera_dir_small) change
 no bit of a frame.
 
 The small-scene kernels take ``camera - centre`` and the sign of the camera's ``c`` from the packer's

@@ -20,7 +20,6 @@ Pass condition: (b)'s median is below (c)'s on both frames.
 
 import argparse
 import json
-import statistics
 import sys
 from pathlib import Path
 
@@ -32,26 +31,10 @@ import torch  # noqa: E402
 import python_ray_tracer_amd.ops  # noqa: E402,F401
 from python_ray_tracer_amd import scenes  # noqa: E402
 from python_ray_tracer_amd.infrastructure.hip import FARAWAY, HipRenderer, _lib as L  # noqa: E402
+from tools.bench_util import summary, timed  # noqa: E402
 
 STREAM_TBPS = 6.3  # achievable HBM streaming rate of the MI355X
 BYTES = {"depth": 8, "id": 4, "hits": 4, "position": 24, "normal": 24, "albedo": 24, "lit": 1}
-
-
-def timed(fn, n):
-    """Per-step times (us) of n calls of fn, one HIP event pair per step."""
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-    for e0, e1 in evs:
-        e0.record()
-        fn()
-        e1.record()
-    torch.cuda.synchronize()
-    return [e0.elapsed_time(e1) * 1e3 for e0, e1 in evs]
-
-
-def summary(us):
-    q = statistics.quantiles(us, n=4)
-    return {"median_us": round(statistics.median(us), 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2),
-            "q1_us": round(q[0], 2), "q3_us": round(q[2], 2), "iqr_us": round(q[2] - q[0], 2), "steps": len(us)}
 
 
 def main():

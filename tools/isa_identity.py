@@ -1,7 +1,7 @@
 """Do two builds of the library's device units hold the same machine code, kernel by kernel?
 
-    for u in rtx_kernels rtx_small rtx_aov rtx_adaptive; do
-      hipcc <_build.HIPCC_FLAGS> --cuda-device-only -S -o DIR/$u.s python_ray_tracer_amd/csrc/$u.hip
+    for f in python_ray_tracer_amd/csrc/*.hip; do       (every *.hip with device code)
+      hipcc <_build.HIPCC_FLAGS> --cuda-device-only -S -o DIR/$(basename $f .hip).s $f
     done                                  (once in a checkout of the old revision, once in the new one)
     python tools/isa_identity.py OLD_DIR NEW_DIR > profiles/split_isa_identity.txt
 

@@ -18,7 +18,6 @@ cost.
 
 import argparse
 import json
-import statistics
 import sys
 from pathlib import Path
 
@@ -29,23 +28,7 @@ import torch  # noqa: E402
 
 from python_ray_tracer_amd import scenes  # noqa: E402
 from python_ray_tracer_amd.infrastructure.hip import HipRenderer  # noqa: E402
-
-
-def timed(fn, n):
-    """Per-step times (us) of n calls of fn, one HIP event pair per step."""
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-    for e0, e1 in evs:
-        e0.record()
-        fn()
-        e1.record()
-    torch.cuda.synchronize()
-    return [e0.elapsed_time(e1) * 1e3 for e0, e1 in evs]
-
-
-def summary(us):
-    q = statistics.quantiles(us, n=4)
-    return {"median_us": round(statistics.median(us), 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2),
-            "q1_us": round(q[0], 2), "q3_us": round(q[2], 2), "iqr_us": round(q[2] - q[0], 2), "steps": len(us)}
+from tools.bench_util import summary, timed  # noqa: E402
 
 
 def main():
