@@ -37,6 +37,9 @@
  *   rtx_trace_glass     <- no counterpart (shader.py:143 "TODO: VOIR TRANSMISSION"): raytrace_scene on
  *                          explicit rays through a scene with solid glass spheres, whose transmitted ray
  *                          is one more level of the recursion, added after the iridescence term
+ *   rtx_trace_lights    <- no counterpart (main.py "TODO: use multiple lights", domain.py "class
+ *                          PointLight:  # TODO: add intensity"): raytrace_scene on explicit rays with
+ *                          every point light of a table, each weighted by intensity * colour
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -68,8 +71,8 @@ extern "C" {
 
 #define RTX_ABI_VERSION 3 /* 2: rtx_resolve_samples; 3: rtx_last_launches, RTX_WS_COUNTER_BYTES */
 /* (rtx_primary_aovs*, rtx_edge_mask, rtx_sample_dirs and rtx_resolve_scatter were added to version 3:
- * new symbols only, nothing that existed changed; so were rtx_camera_rays, rtx_occlusion, and
- * rtx_trace_glass with rtx_glass_workspace_bytes) */
+ * new symbols only, nothing that existed changed; so were rtx_camera_rays, rtx_occlusion,
+ * rtx_trace_glass with rtx_glass_workspace_bytes, and rtx_trace_lights with rtx_lights_workspace_bytes) */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -634,6 +637,59 @@ size_t rtx_glass_workspace_bytes(int64_t n_rays, int max_bounces);
 int rtx_trace_glass(const double* scene, int n_spheres, const double* glass, const double* origins,
                     int64_t origin_stride, const double* dirs, int64_t n, int max_bounces, void* out,
                     int out_kind, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Several point lights with intensity and colour (HipRenderer on a scene whose lights hold a
+ * domain.ColoredPointLight; the reference lights with scene.lights[0] alone, white and
+ * of strength 1: main.py "TODO: use multiple lights", domain.py "class PointLight:  # TODO: add
+ * intensity"): NumpyRenderer.raytrace_scene (base.py:91-121) on n explicit rays, where
+ * NumpyShader.create (shader.py:63-112) sums its light-dependent terms over the rows of `lights`,
+ * double [n_lights][6]: row i is (px, py, pz, e_r, e_g, e_b) with e = intensity * colour per channel
+ * (finite, >= 0), in scene.lights order; it is not part of the scene blob, whose own light
+ * (RTX_H_LIGHT) this entry does not read.
+ * For a hit with point P, normal N and nudged point Q (shader.py:73-77), float64 in this order
+ * exactly, no contraction, for each light i in table order:
+ *     L_i   = norm(pos_i - P)                                              (shader.py:75)
+ *     lit_i = the shadow test along L_i from Q (shader.py:126-128) in its any-hit form: no shape is
+ *             strictly nearer than the hit shape's own distance
+ *     dli_i = max(N.L_i, 0)                                                (shader.py:138)
+ *     spec_i = _calculate_physical_specular with L_i (shader.py:246-320), evaluated only where lit_i
+ *              and g != 0 (g: specular_gain)
+ * and per channel c, with tex the texture's colour, dg the diffuse gain, R the reflected colour one
+ * level deeper, dome and irid the reference's dome-light and iridescence terms (unweighted):
+ *     diffuse[c] = sum_i (((tex[c]*dli_i)*lit_i)*dg)*e_i[c]
+ *     glossy[c]  = sum_i (((spec_i + R[c]*0.5)*g)*lit_i)*e_i[c]
+ *     colour[c]  = (((0.004 + diffuse[c]) + dome[c]) + glossy[c]) + irid[c]
+ * both sums from 0.0 in table order. The reflected ray is traced only if the level is below
+ * max_bounces, g != 0 and some channel of sum_i lit_i*e_i is not 0 (a reflection that is multiplied
+ * by zero is not traced). With one light of e = (1, 1, 1) every added factor is a multiplication by
+ * 1.0 and the colour is the reference's create exactly. Which rays exist, what they hit (the nearest
+ * shape; ties are shaded in scene order, base.py:102-119) and every lit_i are the reference's
+ * decisions bit for bit. A pixel's colour is the sum over its ray tree of W[c] * (the hit's colour
+ * with R = 0), the weight ((W[c]*0.5)*g) * sum_i lit_i*e_i[c] down a reflection: the terms of the
+ * nested sum, reassociated (a few ulp of the colour, as in every render kernel here).
+ * The shadow test walks the culling tree where the scene has one; the light-space shadow grid is
+ * built for lights[0] only and is not used.
+ * One lane per ray; each lane keeps a stack of 2*max_bounces + 2 pending rays (10 words each:
+ * origin, direction, RGB weight, level) in the workspace. A hit pushes at most one ray, so a chain
+ * needs 1 entry, a tree whose every ray meets two shapes at the nearest distance max_bounces + 1 and
+ * one of three shapes 2*max_bounces + 1. A lane that would need more drops the ray and sets
+ * RTX_ST_STACK_OVERFLOW in the workspace's RTX_WS_STATUS word (sticky: the caller reads and clears
+ * it); nothing is written out of bounds. The workspace is RTX_WS_HDR_BYTES of header, zeroed once by
+ * the caller, and the stacks of a bounded pool of workers: rtx_lights_workspace_bytes(n, max_bounces)
+ * does not grow with n beyond that pool (0 for arguments rtx_trace_lights refuses).
+ * out / out_kind as rtx_trace_rays (RTX_OUT_*; uint8 [n][3]). A blob whose magic or sphere count
+ * disagrees with n_spheres makes every ray a miss (colour 0). Asynchronous on `stream`, never
+ * allocates, never synchronises. RTX_E_ARG (before any HIP call) for a null scene, lights, origins,
+ * dirs, out or workspace, n_spheres outside 1..RTX_MAX_SPHERES, n_lights outside
+ * 1..RTX_MAX_POINT_LIGHTS, max_bounces outside 0..RTX_LIGHTS_MAX_BOUNCES, a bad out_kind, a negative
+ * n or an origin_stride other than 0 or n; RTX_E_WORKSPACE for a workspace that is too small; n == 0
+ * returns RTX_OK without a launch. */
+enum { RTX_MAX_POINT_LIGHTS = 8, RTX_LIGHTS_MAX_BOUNCES = 16 };
+size_t rtx_lights_workspace_bytes(int64_t n_rays, int max_bounces);
+int rtx_trace_lights(const double* scene, int n_spheres, const double* lights, int n_lights,
+                     const double* origins, int64_t origin_stride, const double* dirs, int64_t n,
+                     int max_bounces, void* out, int out_kind, void* workspace, size_t workspace_bytes,
+                     void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

@@ -19,6 +19,8 @@
 //                        camera's frame or for explicit rays
 //   rt::trace_glass   <- no counterpart (shader.py:143, "TODO: VOIR TRANSMISSION"): raytrace_scene on explicit rays
 //                        through a scene with solid glass spheres (rtx_trace_glass); allocates its workspace
+//   rt::trace_lights  <- no counterpart (main.py, "TODO: use multiple lights"): raytrace_scene on explicit rays with
+//                        every point light of a table (rtx_trace_lights); allocates its workspace
 //   rt::occlusion     <- no counterpart: ambient occlusion and soft shadows of the primary hit, side x side
 //                        any-hit rays per hit from the id, position and normal passes (rtx_occlusion)
 //   rt::edge_mask, rt::sample_dirs, rt::resolve_scatter
@@ -763,6 +765,58 @@ at::Tensor trace_glass(const at::Tensor& scene, int64_t n_spheres, const at::Ten
   return out;
 }
 
+// ---- several point lights (rtx_trace_lights) ------------------------------------------------------
+// Shapes and ranges of rt::trace_lights's arguments, shared by the kernel and its Meta form: returns n.
+int64_t check_lights(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights, const at::Tensor& origins,
+                     const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind) {
+  check_scene_shape(scene, n_spheres);
+  TORCH_CHECK(lights.scalar_type() == at::kDouble && lights.dim() == 2 && lights.size(1) == 6 &&
+                  lights.size(0) >= 1 && lights.size(0) <= RTX_MAX_POINT_LIGHTS,
+              "lights must be ", at::kDouble, " [L, 6] with L in 1..", (int)RTX_MAX_POINT_LIGHTS,
+              " (lights.lights_table), got ", lights.scalar_type(), " ", lights.sizes());
+  TORCH_CHECK(dirs.scalar_type() == at::kDouble && dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be ", at::kDouble,
+              " [3, n], got ", dirs.scalar_type(), " ", dirs.sizes());
+  const int64_t n = dirs.size(1);
+  TORCH_CHECK(origins.scalar_type() == at::kDouble &&
+                  ((origins.dim() == 1 && origins.numel() == 3) ||
+                   (origins.dim() == 2 && origins.size(0) == 3 && origins.size(1) == n)),
+              "origins must be ", at::kDouble, " [3] (shared) or [3, n] with n = ", n, ", got ", origins.scalar_type(),
+              " ", origins.sizes());
+  TORCH_CHECK(max_bounces >= 0 && max_bounces <= RTX_LIGHTS_MAX_BOUNCES, "max_bounces must lie in 0..",
+              (int)RTX_LIGHTS_MAX_BOUNCES, " (a multi-light scene needs a finite cap), got ", max_bounces);
+  TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA || out_kind == RTX_OUT_U8_HWC,
+              "bad out_kind ", out_kind);
+  return n;
+}
+
+at::Tensor trace_lights(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights, const at::Tensor& origins,
+                        const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind, bool check) {
+  check_gpu(scene, "scene", at::kDouble);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  const struct { const at::Tensor& t; const char* name; } in[] = {{lights, "lights"}, {origins, "origins"}, {dirs, "dirs"}};
+  for (const auto& a : in) {
+    check_gpu(a.t, a.name, at::kDouble);
+    check_same_device(scene, a.t, a.name);
+  }
+  const int64_t n = check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind);
+  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
+  if (check) check_headers(scene, n_spheres);
+  if (n == 0) return out;  // (an empty tensor's pointer may be null)
+  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
+  at::Tensor ws = at::zeros({(int64_t)rtx_lights_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
+  check_rc(rtx_trace_lights(scene.data_ptr<double>(), (int)n_spheres, lights.data_ptr<double>(), (int)lights.size(0),
+                            origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
+                            (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(),
+                            stream_of(scene)),
+           "rtx_trace_lights");
+  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
+    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
+    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
+                2 * max_bounces + 2, " pending rays; HipRenderer raises RecursionError)");
+  }
+  return out;
+}
+
 int64_t status(at::Tensor& workspace) {
   check_gpu(workspace, "workspace", at::kByte);
   TORCH_CHECK(workspace.numel() >= RTX_WS_HDR_BYTES, "workspace shorter than its header");
@@ -951,6 +1005,12 @@ at::Tensor trace_glass_meta(const at::Tensor& scene, int64_t n_spheres, const at
   return new_output(scene, check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
 }
 
+at::Tensor trace_lights_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights,
+                             const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                             bool) {
+  return new_output(scene, check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
+}
+
 at::Tensor edge_mask_meta(const at::Tensor& color, const at::Tensor& id, const at::Tensor& hits,
                           const at::Tensor& lit, int64_t width, int64_t height, double contrast) {
   check_edge_inputs(color, id, hits, lit, width, height, contrast);
@@ -1008,6 +1068,8 @@ TORCH_LIBRARY(rt, m) {
         "float max_distance, float light_radius, int passes, bool check=True) -> Tensor[]");
   m.def("trace_glass(Tensor scene, int n_spheres, Tensor glass, Tensor origins, Tensor dirs, int max_bounces, "
         "int out_kind, bool check=True) -> Tensor");
+  m.def("trace_lights(Tensor scene, int n_spheres, Tensor lights, Tensor origins, Tensor dirs, int max_bounces, "
+        "int out_kind, bool check=True) -> Tensor");
   m.def("edge_mask(Tensor color, Tensor id, Tensor hits, Tensor lit, int width, int height, float contrast) -> Tensor");
   m.def("sample_dirs(Tensor sample_scene, int k, int width, int height, Tensor pixels) -> Tensor");
   m.def("resolve_scatter(Tensor samples, int k, Tensor pixels, int width, int height, Tensor(a!) out, "
@@ -1042,6 +1104,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("primary_aovs_rays", &primary_aovs_rays);
   m.impl("occlusion", &occlusion);
   m.impl("trace_glass", &trace_glass);
+  m.impl("trace_lights", &trace_lights);
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
@@ -1064,6 +1127,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("primary_aovs_rays", &primary_aovs_rays);
   m.impl("occlusion", &occlusion);
   m.impl("trace_glass", &trace_glass);
+  m.impl("trace_lights", &trace_lights);
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
@@ -1084,6 +1148,7 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("primary_aovs_rays", &primary_aovs_rays_meta);
   m.impl("occlusion", &occlusion_meta);
   m.impl("trace_glass", &trace_glass_meta);
+  m.impl("trace_lights", &trace_lights_meta);
   m.impl("edge_mask", &edge_mask_meta);
   m.impl("sample_dirs", &sample_dirs_meta);
   m.impl("resolve_scatter", &resolve_scatter_meta);

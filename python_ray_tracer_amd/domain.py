@@ -72,9 +72,22 @@ class PerspectiveCamera(Camera):
 @dataclass
 class PointLight:
     """Reference ``domain.py:26-30``. Only ``scene.lights[0]`` is ever used as the point light
-    (``shader.py:75``)."""
+    (``shader.py:75``), unless the list holds a ``ColoredPointLight``."""
 
     position: Vector3D
+
+
+@dataclass
+class ColoredPointLight(PointLight):
+    """A point light with a strength and a colour (no counterpart in the reference: ``domain.py`` says
+    "class PointLight:  # TODO: add intensity", ``main.py`` "TODO: use multiple lights"). One of them in
+    ``scene.lights`` makes the scene a multi-light scene: every point light of the list then lights
+    it, in list order, each weighted per channel by ``intensity * color`` (a plain ``PointLight``
+    counts as intensity 1 and white). ``color``: an ``RGBColor`` or three numbers. Validated and
+    reduced to the kernel's table by ``python_ray_tracer_amd.lights``."""
+
+    intensity: float = 1.0
+    color: object = (1.0, 1.0, 1.0)
 
 
 @dataclass

@@ -33,6 +33,8 @@ UNBOUNDED_LEVELS = 333
 MAX_SPHERES = 1024
 MAX_SAMPLES = 8  # samples per pixel side (rtx_resolve_samples)
 GLASS_MAX_BOUNCES = 8  # the largest bounce cap of a transmissive scene (rtx_trace_glass)
+MAX_POINT_LIGHTS = 8  # the rows of a multi-light scene's table (rtx_trace_lights)
+LIGHTS_MAX_BOUNCES = 16  # the largest bounce cap of a multi-light scene (rtx_trace_lights)
 MAGIC = 5527384.0
 UNBOUNDED = -1
 
@@ -117,6 +119,8 @@ EXPORTS = (
     "rtx_occlusion",
     "rtx_glass_workspace_bytes",
     "rtx_trace_glass",
+    "rtx_lights_workspace_bytes",
+    "rtx_trace_lights",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -197,6 +201,9 @@ _SIGS = {
     "rtx_glass_workspace_bytes": (_size, [_i64, _i32]),
     "rtx_trace_glass": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p, _i32,
                                _c_void_p, _size, _c_void_p]),
+    "rtx_lights_workspace_bytes": (_size, [_i64, _i32]),
+    "rtx_trace_lights": (_i32, [_c_void_p, _i32, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p,
+                                _i32, _c_void_p, _size, _c_void_p]),
 }
 
 _lib = None

@@ -58,6 +58,14 @@ that device's current HIP stream and returns a new tensor):
   allocates its own workspace. With ``check=True`` it reads the status word back (a synchronisation) and
   raises "maximum recursion depth exceeded" for a ray tree that overflowed a lane's stack of pending
   rays. Every tensor's dtype, device, contiguity and size is checked.
+* ``rt::trace_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind, check=True)`` —
+  raytrace_scene on explicit rays with every point light of a table (rtx_trace_lights; contract in
+  include/rtx_hip.h): ``lights`` is the device table float64 [L, 6], L in 1..8
+  (``lights.lights_table``: position, intensity * colour), origins [3] (shared) or [3, n],
+  ``max_bounces`` in 0..16; out_kind 0 = float32 [3, n], 1 = float64 [3, n], 2 = uint8 [n, 3]. The op
+  allocates its own workspace. With ``check=True`` it reads the status word back (a synchronisation) and
+  raises "maximum recursion depth exceeded" for a ray tree that overflowed a lane's stack of pending
+  rays. Every tensor's dtype, device, contiguity and size is checked.
 * ``rt::edge_mask(color, id, hits, lit, width, height, contrast)``, ``rt::sample_dirs(sample_scene,
   k, width, height, pixels)`` and ``rt::resolve_scatter(samples, k, pixels, width, height, out,
   out_kind)`` — the three steps of adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True);
@@ -104,7 +112,7 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
+       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "trace_lights", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
        "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
        "comm_unique_id", "comm_init", "comm_destroy", "tiles_create", "tiles_submit", "tiles_finish",

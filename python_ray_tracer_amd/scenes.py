@@ -24,6 +24,8 @@ Spec layout::
                   (or {"kind": "image", "texels": (H, W, 3) float colours} — ImageTexture)
                   (a shader may also carry "transmission_gain" and "specular_ior": glass, glass_spec)
      "lights": [{"kind": "point", "position": [x, y, z]},
+                (a point entry may also carry "intensity" and/or "color": [r, g, b]; either makes it a
+                 domain.ColoredPointLight and the scene a multi-light scene, lights_spec)
                 {"kind": "dome", "intensity": i, "color": [r, g, b]}],
      "camera": {"position": [x, y, z], "width": W, "height": H}}
                 (with "target": [x, y, z] a domain.PerspectiveCamera; then also, all optional,
@@ -101,6 +103,19 @@ def glass_spec(width: int = 1920, height: int = 1080) -> dict:
     spec = readme_spec(width, height)
     spec["spheres"][1]["shader"].update(transmission_gain=0.9, diffuse_gain=0.1)
     spec["spheres"][0]["shader"].update(transmission_gain=0.5)
+    return spec
+
+
+def lights_spec(width: int = 1920, height: int = 1080) -> dict:
+    """The README scene under three point lights: its own light stays ``lights[0]`` (a plain point light:
+    intensity 1, white), a warm fill light stands on the other side, behind the spheres, and a blue one
+    above them. The
+    multi-light frame of tools/lights_bench.py, the README and the tests (``rtx_trace_lights``)."""
+    spec = readme_spec(width, height)
+    spec["lights"] += [
+        {"kind": "point", "position": [-1.33, 8.16, 7.23], "intensity": 0.6, "color": [1.0, 0.7, 0.4]},
+        {"kind": "point", "position": [0.18, 9.4, 3.89], "intensity": 0.4, "color": [0.4, 0.6, 1.0]},
+    ]
     return spec
 
 
@@ -198,7 +213,7 @@ CONFIGS = {
 
 def build_scene(spec: dict):
     """Instantiate ``spec`` with this package's HIP-backend classes."""
-    from python_ray_tracer_amd.domain import Camera, DomeLight, PointLight, Scene3D
+    from python_ray_tracer_amd.domain import Camera, ColoredPointLight, DomeLight, PointLight, Scene3D
     from python_ray_tracer_amd.infrastructure.hip import (
         HipRGBColor,
         HipShader,
@@ -228,7 +243,11 @@ def build_scene(spec: dict):
     lights = []
     for li in spec["lights"]:
         if li["kind"] == "point":
-            lights.append(PointLight(HipVector3D(*li["position"])))
+            if "intensity" in li or "color" in li:  # optional: a multi-light scene (lights_spec)
+                lights.append(ColoredPointLight(HipVector3D(*li["position"]), li.get("intensity", 1.0),
+                                                HipRGBColor(*li.get("color", (1.0, 1.0, 1.0)))))
+            else:
+                lights.append(PointLight(HipVector3D(*li["position"])))
         else:
             lights.append(DomeLight(li["intensity"], HipRGBColor(*li["color"])))
     cam = spec["camera"]
