@@ -40,6 +40,9 @@
  *   rtx_trace_lights    <- no counterpart (main.py "TODO: use multiple lights", domain.py "class
  *                          PointLight:  # TODO: add intensity"): raytrace_scene on explicit rays with
  *                          every point light of a table, each weighted by intensity * colour
+ *   rtx_env_sample, rtx_trace_lights_env, rtx_trace_glass_env
+ *                       <- no counterpart (raytrace_scene adds nothing on a miss, base.py:100-121): an
+ *                          equirectangular environment map that every ray which meets no shape samples
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -72,7 +75,8 @@ extern "C" {
 #define RTX_ABI_VERSION 3 /* 2: rtx_resolve_samples; 3: rtx_last_launches, RTX_WS_COUNTER_BYTES */
 /* (rtx_primary_aovs*, rtx_edge_mask, rtx_sample_dirs and rtx_resolve_scatter were added to version 3:
  * new symbols only, nothing that existed changed; so were rtx_camera_rays, rtx_occlusion,
- * rtx_trace_glass with rtx_glass_workspace_bytes, and rtx_trace_lights with rtx_lights_workspace_bytes) */
+ * rtx_trace_glass with rtx_glass_workspace_bytes, and rtx_trace_lights with rtx_lights_workspace_bytes,
+ * and rtx_env_sample, rtx_trace_lights_env and rtx_trace_glass_env) */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -690,6 +694,58 @@ int rtx_trace_lights(const double* scene, int n_spheres, const double* lights, i
                      const double* origins, int64_t origin_stride, const double* dirs, int64_t n,
                      int max_bounces, void* out, int out_kind, void* workspace, size_t workspace_bytes,
                      void* stream);
+
+/* An environment map (HipRenderer on a scene whose lights hold a domain.EnvironmentLight; DESIGN.md
+ * §16; the reference's raytrace_scene starts from black and adds nothing on a miss, base.py:100-121,
+ * and its render settings carry a "background" image that nothing reads): raytrace_scene(O, D) of a
+ * ray whose nearest distance is FARAWAY returns env(D) instead of black, at every level: camera rays,
+ * reflected rays and rays that leave a glass ball. Nothing else changes: the reflected colour still
+ * carries * 0.5 * g * lit (shader.py:106), a ray that is not traced (at the cap, unlit, g == 0) still
+ * contributes nothing, and the dome light, the shadows and the passes do not see the environment.
+ * The image is `texels`, float [height][width][4] on the device (RGB and a zero word; values above 1
+ * are allowed: an HDR sky), 16-byte aligned, at most RTX_ENV_MAX_TEXELS texels, equirectangular: column
+ * by longitude about +y, row 0 at the zenith. gain[c] = intensity * colour[c] and turn = rotation / 360
+ * (rotation in degrees about +y) are computed by the host in float64. rtx_env_t is read on the host at
+ * the call; only `texels` must stay alive until the work has run.
+ * env(D), float64 in this order exactly, no contraction, texels t converted from float32 exactly,
+ * atan2 and asin the device library's (a few ulp, like NumPy's):
+ *     u = 0.5 + atan2(D.z, D.x) / (2 pi) + turn;   u = u - floor(u)
+ *     v = 0.5 - asin(min(max(D.y, -1), 1)) / pi
+ *     x = u*W - 0.5;  i0 = floor(x);  fx = x - i0;  i1 = (i0 + 1) mod W;  i0 = i0 mod W     (wraps)
+ *     y = v*H - 0.5;  j0 = floor(y);  fy = y - j0;  j1 = clamp(j0 + 1, 0, H-1);  j0 = clamp(j0, 0, H-1)
+ *     top = t[j0][i0]*(1 - fx) + t[j0][i1]*fx;   bot = t[j1][i0]*(1 - fx) + t[j1][i1]*fx
+ *     env[c] = (top*(1 - fy) + bot*fy) * gain[c]
+ * (min / max propagate a NaN, as NumPy's do.) If u or v is not finite, env = (0, 0, 0). The lookup is
+ * bilinear so that it is continuous in u and v, across the seam and across texel boundaries: the few
+ * ulp between the device's atan2 / asin and NumPy's move a colour by about as much, not by a texel.
+ * rtx_env_sample: out[c][i] = env(dirs[.][i])[c] for n directions, both double [3][n], one lane per
+ * direction: the lookup alone (a background plate; tests).
+ * rtx_trace_lights_env / rtx_trace_glass_env: rtx_trace_lights / rtx_trace_glass, arguments, workspace
+ * (rtx_lights_workspace_bytes / rtx_glass_workspace_bytes), stacks, status word and errors unchanged,
+ * where a popped ray that meets no shape adds W[c] * env(D)[c] to its pixel's sum (W: the forward-folded
+ * weight of that ray, per channel in the lights kernel), by the kernel's own kind of sum (multiply and
+ * add in the lights kernel, one fused multiply-add in the glass kernel, as their hits). A blob whose
+ * magic or sphere count disagrees with n_spheres makes every ray a miss: every ray then returns env(D).
+ * RTX_E_ARG (before any HIP call) additionally for a null env or texels, width or height < 1, more than
+ * RTX_ENV_MAX_TEXELS texels, a texel pointer that is not 16-byte aligned, a gain or turn that is not
+ * finite; rtx_env_sample also for a null dirs or out or a negative n. n == 0 returns RTX_OK without a
+ * launch. */
+enum { RTX_ENV_MAX_TEXELS = 1 << 23 };
+typedef struct rtx_env_t {
+  const float* texels; /* device, [height][width][4] */
+  int width, height;
+  double gain[3];
+  double turn;
+} rtx_env_t;
+int rtx_env_sample(const rtx_env_t* env, const double* dirs, int64_t n, double* out, void* stream);
+int rtx_trace_lights_env(const double* scene, int n_spheres, const double* lights, int n_lights,
+                         const double* origins, int64_t origin_stride, const double* dirs, int64_t n,
+                         int max_bounces, void* out, int out_kind, void* workspace, size_t workspace_bytes,
+                         void* stream, const rtx_env_t* env);
+int rtx_trace_glass_env(const double* scene, int n_spheres, const double* glass, const double* origins,
+                        int64_t origin_stride, const double* dirs, int64_t n, int max_bounces, void* out,
+                        int out_kind, void* workspace, size_t workspace_bytes, void* stream,
+                        const rtx_env_t* env);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

@@ -21,6 +21,9 @@
 //                        through a scene with solid glass spheres (rtx_trace_glass); allocates its workspace
 //   rt::trace_lights  <- no counterpart (main.py, "TODO: use multiple lights"): raytrace_scene on explicit rays with
 //                        every point light of a table (rtx_trace_lights); allocates its workspace
+//   rt::env_sample, rt::trace_lights_env, rt::trace_glass_env
+//                     <- no counterpart (raytrace_scene adds nothing on a miss, base.py:100-121): the environment
+//                        map's lookup alone, and the two kernels above with it for every ray that meets no shape
 //   rt::occlusion     <- no counterpart: ambient occlusion and soft shadows of the primary hit, side x side
 //                        any-hit rays per hit from the id, position and normal passes (rtx_occlusion)
 //   rt::edge_mask, rt::sample_dirs, rt::resolve_scatter
@@ -61,6 +64,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <cmath>
 #include <mutex>
 #include <optional>
 #include <tuple>
@@ -817,6 +821,113 @@ at::Tensor trace_lights(const at::Tensor& scene, int64_t n_spheres, const at::Te
   return out;
 }
 
+// ---- the environment map (rtx_env_sample, rtx_trace_lights_env, rtx_trace_glass_env) ----------------
+// Shapes and ranges of an environment's arguments, shared by the kernels and their Meta forms: texels
+// float32 [H, W, 4], gain three finite numbers, turn finite. Fills env but for its device pointer.
+void check_env(const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, rtx_env_t& env) {
+  TORCH_CHECK(texels.scalar_type() == at::kFloat && texels.dim() == 3 && texels.size(2) == 4 && texels.size(0) >= 1 &&
+                  texels.size(1) >= 1 && texels.size(0) * texels.size(1) <= RTX_ENV_MAX_TEXELS,
+              "texels must be ", at::kFloat, " [H, W, 4] with 1 <= H * W <= ", (int)RTX_ENV_MAX_TEXELS, ", got ",
+              texels.scalar_type(), " ", texels.sizes());
+  TORCH_CHECK(gain.size() == 3 && std::isfinite(gain[0]) && std::isfinite(gain[1]) && std::isfinite(gain[2]),
+              "gain must be three finite numbers (intensity * colour)");
+  TORCH_CHECK(std::isfinite(turn), "turn must be finite (rotation / 360), got ", turn);
+  env.texels = nullptr;
+  env.height = (int)texels.size(0);
+  env.width = (int)texels.size(1);
+  for (int c = 0; c < 3; ++c) env.gain[c] = gain[c];
+  env.turn = turn;
+}
+
+int64_t check_env_dirs(const at::Tensor& dirs) {
+  TORCH_CHECK(dirs.scalar_type() == at::kDouble && dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be ", at::kDouble,
+              " [3, n], got ", dirs.scalar_type(), " ", dirs.sizes());
+  return dirs.size(1);
+}
+
+at::Tensor env_sample(const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, const at::Tensor& dirs) {
+  check_gpu(texels, "texels", at::kFloat);
+  const at::OptionalDeviceGuard guard(at::device_of(texels));
+  check_gpu(dirs, "dirs", at::kDouble);
+  check_same_device(texels, dirs, "dirs");
+  rtx_env_t env;
+  check_env(texels, gain, turn, env);
+  const int64_t n = check_env_dirs(dirs);
+  at::Tensor out = at::empty({3, n}, dirs.options());
+  if (n == 0) return out;  // (an empty tensor's pointer may be null)
+  env.texels = texels.data_ptr<float>();
+  check_rc(rtx_env_sample(&env, dirs.data_ptr<double>(), n, out.data_ptr<double>(), stream_of(texels)), "rtx_env_sample");
+  return out;
+}
+
+at::Tensor trace_lights_env(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights,
+                            const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                            const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, bool check) {
+  check_gpu(scene, "scene", at::kDouble);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  const struct { const at::Tensor& t; const char* name; } in[] = {{lights, "lights"}, {origins, "origins"}, {dirs, "dirs"}};
+  for (const auto& a : in) {
+    check_gpu(a.t, a.name, at::kDouble);
+    check_same_device(scene, a.t, a.name);
+  }
+  check_gpu(texels, "texels", at::kFloat);
+  check_same_device(scene, texels, "texels");
+  const int64_t n = check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind);
+  rtx_env_t env;
+  check_env(texels, gain, turn, env);
+  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
+  if (check) check_headers(scene, n_spheres);
+  if (n == 0) return out;  // (an empty tensor's pointer may be null)
+  env.texels = texels.data_ptr<float>();
+  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
+  at::Tensor ws = at::zeros({(int64_t)rtx_lights_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
+  check_rc(rtx_trace_lights_env(scene.data_ptr<double>(), (int)n_spheres, lights.data_ptr<double>(), (int)lights.size(0),
+                                origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
+                                (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(),
+                                stream_of(scene), &env),
+           "rtx_trace_lights_env");
+  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
+    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
+    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
+                2 * max_bounces + 2, " pending rays; HipRenderer raises RecursionError)");
+  }
+  return out;
+}
+
+at::Tensor trace_glass_env(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass,
+                           const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                           const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, bool check) {
+  check_gpu(scene, "scene", at::kDouble);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  const struct { const at::Tensor& t; const char* name; } in[] = {{glass, "glass"}, {origins, "origins"}, {dirs, "dirs"}};
+  for (const auto& a : in) {
+    check_gpu(a.t, a.name, at::kDouble);
+    check_same_device(scene, a.t, a.name);
+  }
+  check_gpu(texels, "texels", at::kFloat);
+  check_same_device(scene, texels, "texels");
+  const int64_t n = check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind);
+  rtx_env_t env;
+  check_env(texels, gain, turn, env);
+  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
+  if (check) check_headers(scene, n_spheres);
+  if (n == 0) return out;  // (an empty tensor's pointer may be null)
+  env.texels = texels.data_ptr<float>();
+  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
+  at::Tensor ws = at::zeros({(int64_t)rtx_glass_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
+  check_rc(rtx_trace_glass_env(scene.data_ptr<double>(), (int)n_spheres, glass.data_ptr<double>(),
+                               origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
+                               (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(),
+                               stream_of(scene), &env),
+           "rtx_trace_glass_env");
+  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
+    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
+    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
+                4 * max_bounces + 4, " pending rays; HipRenderer raises RecursionError)");
+  }
+  return out;
+}
+
 int64_t status(at::Tensor& workspace) {
   check_gpu(workspace, "workspace", at::kByte);
   TORCH_CHECK(workspace.numel() >= RTX_WS_HDR_BYTES, "workspace shorter than its header");
@@ -1011,6 +1122,30 @@ at::Tensor trace_lights_meta(const at::Tensor& scene, int64_t n_spheres, const a
   return new_output(scene, check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
 }
 
+at::Tensor env_sample_meta(const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, const at::Tensor& dirs) {
+  rtx_env_t env;
+  check_env(texels, gain, turn, env);
+  return at::empty({3, check_env_dirs(dirs)}, dirs.options());
+}
+
+at::Tensor trace_lights_env_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights,
+                                 const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces,
+                                 int64_t out_kind, const at::Tensor& texels, c10::ArrayRef<double> gain, double turn,
+                                 bool) {
+  rtx_env_t env;
+  check_env(texels, gain, turn, env);
+  return new_output(scene, check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
+}
+
+at::Tensor trace_glass_env_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass,
+                                const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces,
+                                int64_t out_kind, const at::Tensor& texels, c10::ArrayRef<double> gain, double turn,
+                                bool) {
+  rtx_env_t env;
+  check_env(texels, gain, turn, env);
+  return new_output(scene, check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
+}
+
 at::Tensor edge_mask_meta(const at::Tensor& color, const at::Tensor& id, const at::Tensor& hits,
                           const at::Tensor& lit, int64_t width, int64_t height, double contrast) {
   check_edge_inputs(color, id, hits, lit, width, height, contrast);
@@ -1070,6 +1205,11 @@ TORCH_LIBRARY(rt, m) {
         "int out_kind, bool check=True) -> Tensor");
   m.def("trace_lights(Tensor scene, int n_spheres, Tensor lights, Tensor origins, Tensor dirs, int max_bounces, "
         "int out_kind, bool check=True) -> Tensor");
+  m.def("env_sample(Tensor texels, float[] gain, float turn, Tensor dirs) -> Tensor");
+  m.def("trace_lights_env(Tensor scene, int n_spheres, Tensor lights, Tensor origins, Tensor dirs, int max_bounces, "
+        "int out_kind, Tensor texels, float[] gain, float turn, bool check=True) -> Tensor");
+  m.def("trace_glass_env(Tensor scene, int n_spheres, Tensor glass, Tensor origins, Tensor dirs, int max_bounces, "
+        "int out_kind, Tensor texels, float[] gain, float turn, bool check=True) -> Tensor");
   m.def("edge_mask(Tensor color, Tensor id, Tensor hits, Tensor lit, int width, int height, float contrast) -> Tensor");
   m.def("sample_dirs(Tensor sample_scene, int k, int width, int height, Tensor pixels) -> Tensor");
   m.def("resolve_scatter(Tensor samples, int k, Tensor pixels, int width, int height, Tensor(a!) out, "
@@ -1105,6 +1245,9 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("occlusion", &occlusion);
   m.impl("trace_glass", &trace_glass);
   m.impl("trace_lights", &trace_lights);
+  m.impl("env_sample", &env_sample);
+  m.impl("trace_lights_env", &trace_lights_env);
+  m.impl("trace_glass_env", &trace_glass_env);
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
@@ -1128,6 +1271,9 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("occlusion", &occlusion);
   m.impl("trace_glass", &trace_glass);
   m.impl("trace_lights", &trace_lights);
+  m.impl("env_sample", &env_sample);
+  m.impl("trace_lights_env", &trace_lights_env);
+  m.impl("trace_glass_env", &trace_glass_env);
   m.impl("edge_mask", &edge_mask);
   m.impl("sample_dirs", &sample_dirs);
   m.impl("resolve_scatter", &resolve_scatter);
@@ -1149,6 +1295,9 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("occlusion", &occlusion_meta);
   m.impl("trace_glass", &trace_glass_meta);
   m.impl("trace_lights", &trace_lights_meta);
+  m.impl("env_sample", &env_sample_meta);
+  m.impl("trace_lights_env", &trace_lights_env_meta);
+  m.impl("trace_glass_env", &trace_glass_env_meta);
   m.impl("edge_mask", &edge_mask_meta);
   m.impl("sample_dirs", &sample_dirs_meta);
   m.impl("resolve_scatter", &resolve_scatter_meta);

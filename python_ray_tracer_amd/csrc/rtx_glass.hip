@@ -8,6 +8,7 @@
 // render kernels compile from untouched text with untouched flags.
 #include "rtx_device.h"
 #include "rtx_internal.h"
+#include "rtx_env.h"
 
 namespace {
 
@@ -106,109 +107,25 @@ __device__ __forceinline__ void through_ball(double px, double py, double pz, do
 // need a new ray pop and search together (the search loops are wave-uniform, the sphere table comes
 // through the scalar cache); a lane at a tie (several shapes at the nearest distance, base.py:102-119)
 // shades them one per round in scene order.
+// The kernel's body is rtx_glass_walk.inc, included below into k_trace_glass (ENV false: the kernel as it was)
+// and into k_trace_glass_env (ENV true: a popped ray that meets no shape adds env(D), rtx_env.h, before the
+// lane goes on; the lookup runs where little is live, after the pop and before any shade).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kGlassWaves, kGlassWaves)))
 void k_trace_glass(GlassParams p) {
-  const int64_t w = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (w >= p.n_workers) return;
-  const cdouble* sc = (const cdouble*)p.scene;
-  // a blob that is not a packed scene of p.nsph spheres: every ray a miss
-  const int nsph = (sc[RTX_H_MAGIC] == RTX_MAGIC && sc[RTX_H_NSPH] == (double)p.nsph) ? p.nsph : 0;
-  const cdouble* geo = sc + RTX_HDR_WORDS;
-  const double* tab = p.scene + RTX_HDR_WORDS;
-  const double* mtab = tab + nsph * RTX_GEOM_WORDS;
-  const int B = p.max_bounces;
-  const int cap = glass_stack_entries(B);
-  const bool tree = sc[RTX_H_NNODES] != 0.0 && nsph >= kGeneralTreeMin;
-  const double nan = __builtin_nan("");  // the reference expressions in every sphere test (SphTest)
-  const RayStack S{p.stack, p.n_workers, w};
-  Params po{};  // what write_out reads
-  po.out = p.out;
-  po.out_kind = p.out_kind;
-  po.n = p.n;
-  for (int64_t i = w; i < p.n; i += p.n_workers) {
-    {
-      const int64_t s = p.org_stride;
-      const int64_t j = s ? i : 0;
-      S.push(0, p.org[j], p.org[s + j + (s ? 0 : 1)], p.org[2 * s + j + (s ? 0 : 2)], p.dir[i], p.dir[p.n + i],
-             p.dir[2 * p.n + i], 1.0, 0);
-    }
-    int sp = 1;  // pending rays
-    double ar = 0.0, ag = 0.0, ab = 0.0;
-    // the ray whose hits are being shaded: `left` of them to go, the next one at or after shape `next`
-    double ox = 0.0, oy = 0.0, oz = 0.0, dx = 0.0, dy = 0.0, dz = 0.0, oo = 0.0, wt = 0.0, tmin = FARAWAY;
-    int level = 0, left = 0, next = 0;
-    for (;;) {
-      int h = nsph;
-      if (left == 0) {
-        if (sp == 0) break;
-        --sp;
-        ox = S.at(sp, 0); oy = S.at(sp, 1); oz = S.at(sp, 2);
-        dx = S.at(sp, 3); dy = S.at(sp, 4); dz = S.at(sp, 5);
-        wt = S.at(sp, 6);
-        level = (int)S.at(sp, 7);
-        oo = dot3(ox, oy, oz, ox, oy, oz);
-        // the nearest distance (base.py:97-98), how many shapes share it and the first in scene order
-        tmin = FARAWAY;
-        int nh = 0, first = nsph;
-        nearest_count(sc, nsph, tree, ox, oy, oz, oo, dx, dy, dz, tmin, nh, first);
-        left = tmin != FARAWAY ? nh : 0;  // (nearest != FARAWAY) & (t == nearest), base.py:102-103
-        if (left == 0) continue;
-        h = first;
-      } else {  // a tie: the next shape in scene order at the nearest distance
-        for (int s = next; s < nsph; ++s) {
-          if (isect(tab + s * RTX_GEOM_WORDS, ox, oy, oz, oo, dx, dy, dz) == tmin) {
-            h = s;
-            break;
-          }
-        }
-        if (h == nsph) {  // (cannot happen: `left` counted it)
-          left = 0;
-          continue;
-        }
-      }
-      next = h + 1;
-      --left;
-      Hit s;
-      Work<false> nowk;
-      shade<true>(sc, geo, tab, nsph, h, ox, oy, oz, dx, dy, dz, tmin, s, nan, nowk);
-      const bool weighted = s.lit && s.g != 0.0;
-      double xr, xg, xb;
-      hit_color<true>(mtab + h * RTX_MAT_WORDS, sc, s.dli, s.di, s.tk, s.lit, weighted, s.spec, s.va, 0.0, 0.0, 0.0,
-                      xr, xg, xb);
-      ar = __builtin_fma(wt, xr, ar);
-      ag = __builtin_fma(wt, xg, ag);
-      ab = __builtin_fma(wt, xb, ab);
-      if (level >= B) continue;  // the next level is black
-      if (weighted) {  // the reflected ray, (R * 0.5) * g (shader.py:106)
-        if (sp < cap) {
-          double rx = dx, ry = dy, rz = dz;
-          reflect_dir(rx, ry, rz, s.nx, s.ny, s.nz);
-          S.push(sp, s.qx, s.qy, s.qz, rx, ry, rz, (wt * 0.5) * s.g, level + 1);
-          ++sp;
-        } else {
-          atomicOr(p.status, (uint32_t)RTX_ST_STACK_OVERFLOW);
-        }
-      }
-      const double tg = p.glass[h];
-      if (tg != 0.0) {
-        const double c = dot3(dx, dy, dz, s.nx, s.ny, s.nz);
-        if (c < 0.0) {  // met from outside (a hit from inside gets no transmitted ray)
-          if (sp < cap) {
-            const double* gh = tab + h * RTX_GEOM_WORDS;
-            const double px = ox + dx * tmin, py = oy + dy * tmin, pz = oz + dz * tmin;  // :73, as shade has it
-            double qx, qy, qz, rx, ry, rz;
-            through_ball(px, py, pz, dx, dy, dz, s.nx, s.ny, s.nz, c, gh[RTX_G_CX], gh[RTX_G_CY], gh[RTX_G_CZ],
-                         gh[RTX_G_INVR], p.glass[nsph + h], qx, qy, qz, rx, ry, rz);
-            S.push(sp, qx, qy, qz, rx, ry, rz, wt * tg, level + 1);
-            ++sp;
-          } else {
-            atomicOr(p.status, (uint32_t)RTX_ST_STACK_OVERFLOW);
-          }
-        }
-      }
-    }
-    write_out(po, i, ar, ag, ab);
-  }
+  constexpr bool ENV = false;
+  const EnvFields env{};  // (not read)
+#include "rtx_glass_walk.inc"
+}
+
+struct GlassEnvParams : GlassParams {
+  EnvFields env;
+};
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kGlassWaves, kGlassWaves)))
+void k_trace_glass_env(GlassEnvParams p) {
+  constexpr bool ENV = true;
+  const EnvFields& env = p.env;
+#include "rtx_glass_walk.inc"
 }
 
 }  // namespace
@@ -219,9 +136,12 @@ extern "C" size_t rtx_glass_workspace_bytes(int64_t n_rays, int max_bounces) {
          (size_t)glass_workers(n_rays, max_bounces) * glass_stack_entries(max_bounces) * kRayWords * 8;
 }
 
-extern "C" int rtx_trace_glass(const double* scene, int n_spheres, const double* glass, const double* origins,
-                               int64_t origin_stride, const double* dirs, int64_t n, int max_bounces, void* out,
-                               int out_kind, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+
+// rtx_trace_glass (with_env false: env is not read) and rtx_trace_glass_env behind one set of checks
+int trace_glass_call(const double* scene, int n_spheres, const double* glass, const double* origins,
+                     int64_t origin_stride, const double* dirs, int64_t n, int max_bounces, void* out, int out_kind,
+                     void* workspace, size_t workspace_bytes, void* stream, bool with_env, const rtx_env_t* env) {
   if (!scene) return rtx_fail(RTX_E_ARG, "null scene pointer");
   if (!glass) return rtx_fail(RTX_E_ARG, "null glass table pointer");
   if (!origins || !dirs) return rtx_fail(RTX_E_ARG, "null ray pointer (origins, dirs)");
@@ -240,8 +160,10 @@ extern "C" int rtx_trace_glass(const double* scene, int n_spheres, const double*
   if (workspace_bytes < need)
     return rtx_fail(RTX_E_WORKSPACE, "workspace too small: %zu < %zu bytes (rtx_glass_workspace_bytes)",
                     workspace_bytes, need);
+  GlassEnvParams p{};
+  if (with_env)
+    if (const int rc = env_fields(env, p.env)) return rc;
   if (n == 0) return RTX_OK;
-  GlassParams p{};
   p.scene = scene;
   p.nsph = n_spheres;
   p.glass = glass;
@@ -255,6 +177,28 @@ extern "C" int rtx_trace_glass(const double* scene, int n_spheres, const double*
   p.status = (uint32_t*)workspace + RTX_WS_STATUS;
   p.stack = (double*)((uint8_t*)workspace + RTX_WS_HDR_BYTES);
   p.n_workers = glass_workers(n, max_bounces);
-  hipLaunchKernelGGL(k_trace_glass, dim3((unsigned)(p.n_workers / 64)), dim3(64), 0, (hipStream_t)stream, p);
+  const dim3 grid((unsigned)(p.n_workers / 64));
+  if (with_env) {
+    hipLaunchKernelGGL(k_trace_glass_env, grid, dim3(64), 0, (hipStream_t)stream, p);
+    return rtx_launched("k_trace_glass_env");
+  }
+  hipLaunchKernelGGL(k_trace_glass, grid, dim3(64), 0, (hipStream_t)stream, (const GlassParams&)p);
   return rtx_launched("k_trace_glass");
+}
+
+}  // namespace
+
+extern "C" int rtx_trace_glass(const double* scene, int n_spheres, const double* glass, const double* origins,
+                               int64_t origin_stride, const double* dirs, int64_t n, int max_bounces, void* out,
+                               int out_kind, void* workspace, size_t workspace_bytes, void* stream) {
+  return trace_glass_call(scene, n_spheres, glass, origins, origin_stride, dirs, n, max_bounces, out, out_kind,
+                          workspace, workspace_bytes, stream, false, nullptr);
+}
+
+extern "C" int rtx_trace_glass_env(const double* scene, int n_spheres, const double* glass, const double* origins,
+                                   int64_t origin_stride, const double* dirs, int64_t n, int max_bounces, void* out,
+                                   int out_kind, void* workspace, size_t workspace_bytes, void* stream,
+                                   const rtx_env_t* env) {
+  return trace_glass_call(scene, n_spheres, glass, origins, origin_stride, dirs, n, max_bounces, out, out_kind,
+                          workspace, workspace_bytes, stream, true, env);
 }

@@ -313,11 +313,14 @@ def tile_gather_for(renderer, scene, *, group=None, row_block: int = 8, dst: int
     W, H = int(scene.camera.width), int(scene.camera.height)
     # a PerspectiveCamera's tile is generated rays traced by render_tile: the native plan (rtx_tiles_submit)
     # renders the reference camera, so such scenes take render_tile(into=) and the gather, like supersampling;
-    # so does a multi-light scene, whose rays are traced by rtx_trace_lights (submit_tiles refuses it)
+    # so does a multi-light scene, whose rays are traced by rtx_trace_lights (submit_tiles refuses it), and an
+    # environment scene (rtx_trace_lights_env / rtx_trace_glass_env)
     from python_ray_tracer_amd.camera import is_perspective
+    from python_ray_tracer_amd.environment import environment_of
     from python_ray_tracer_amd.lights import is_multi_light
 
-    native = False if is_perspective(scene.camera) or is_multi_light(scene.lights) else None
+    explicit = is_perspective(scene.camera) or is_multi_light(scene.lights) or environment_of(scene.lights) is not None
+    native = False if explicit else None
     key = (W, H, int(row_block), int(dst), "u8" if out == "u8" else None, id(group), dist.get_world_size(group),
            getattr(renderer, "color_dtype", None), native)
     cache = getattr(renderer, "_tile_gathers", None)

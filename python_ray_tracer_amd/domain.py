@@ -90,6 +90,37 @@ class ColoredPointLight(PointLight):
     color: object = (1.0, 1.0, 1.0)
 
 
+class EnvironmentLight:
+    """An environment map: what a ray that meets no shape sees (no counterpart in the reference, whose
+    ``raytrace_scene`` adds nothing on a miss, base.py:100-121; its render settings carry a "background"
+    image that nothing reads). One of them in ``scene.lights`` makes the scene an environment scene:
+    camera rays, reflected rays and rays that leave a glass ball then return the image's colour in
+    their direction where they meet nothing. It lights no surface (the dome light and the shadows do
+    not see it) and has no ``position``, so it cannot be ``lights[0]``.
+
+    ``image``: an equirectangular picture, columns by longitude about +y and row 0 at the zenith: a
+    path (opened with PIL, ``convert("RGB")``, ``/ 255.0``), an (H, W, 3) uint8 array (``/ 255.0``) or an
+    (H, W, 3) float array, whose values may exceed 1 (an HDR sky). At most 2^23 texels, none negative
+    or not finite (ValueError). The light keeps ``texels``, a read-only float32 copy [H, W, 4] (RGB and a
+    zero word: one 128-bit load per tap on the device), and ``digest``, its content hash, computed
+    once. ``intensity`` and ``color`` (an ``RGBColor`` or three numbers) scale the image per channel;
+    ``rotation`` turns it about +y, in degrees. Validated and reduced to the kernel's arguments by
+    ``python_ray_tracer_amd.environment``."""
+
+    def __init__(self, image, intensity: float = 1.0, color=(1.0, 1.0, 1.0), rotation: float = 0.0) -> None:
+        from python_ray_tracer_amd.environment import image_texels
+
+        self.texels, self.digest = image_texels(image)
+        self.intensity = intensity
+        self.color = color
+        self.rotation = rotation
+
+    def __repr__(self) -> str:
+        h, w = self.texels.shape[:2]
+        return (f"EnvironmentLight(<{w} x {h} image {self.digest[:8]}>, intensity={self.intensity!r}, "
+                f"color={self.color!r}, rotation={self.rotation!r})")
+
+
 @dataclass
 class DomeLight:
     """Sky light (reference ``domain.py:33-40``); every DomeLight in ``scene.lights`` adds its

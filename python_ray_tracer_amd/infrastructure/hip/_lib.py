@@ -35,6 +35,7 @@ MAX_SAMPLES = 8  # samples per pixel side (rtx_resolve_samples)
 GLASS_MAX_BOUNCES = 8  # the largest bounce cap of a transmissive scene (rtx_trace_glass)
 MAX_POINT_LIGHTS = 8  # the rows of a multi-light scene's table (rtx_trace_lights)
 LIGHTS_MAX_BOUNCES = 16  # the largest bounce cap of a multi-light scene (rtx_trace_lights)
+ENV_MAX_TEXELS = 1 << 23  # the largest environment image (rtx_env_t)
 MAGIC = 5527384.0
 UNBOUNDED = -1
 
@@ -121,6 +122,9 @@ EXPORTS = (
     "rtx_trace_glass",
     "rtx_lights_workspace_bytes",
     "rtx_trace_lights",
+    "rtx_env_sample",
+    "rtx_trace_lights_env",
+    "rtx_trace_glass_env",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -144,6 +148,17 @@ _c_void_p = ctypes.c_void_p
 _i32 = ctypes.c_int
 _i64 = ctypes.c_int64
 _size = ctypes.c_size_t
+
+
+
+class Env(ctypes.Structure):
+    """rtx_env_t: the environment map a call reads on the host (texels: a device pointer)."""
+
+    _fields_ = [("texels", _c_void_p), ("width", _i32), ("height", _i32), ("gain", ctypes.c_double * 3),
+                ("turn", ctypes.c_double)]
+
+
+_env_p = ctypes.POINTER(Env)
 
 _SIGS = {
     "rtx_abi_version": (_i32, [ctypes.POINTER(_i32), _i32]),
@@ -204,6 +219,11 @@ _SIGS = {
     "rtx_lights_workspace_bytes": (_size, [_i64, _i32]),
     "rtx_trace_lights": (_i32, [_c_void_p, _i32, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p,
                                 _i32, _c_void_p, _size, _c_void_p]),
+    "rtx_env_sample": (_i32, [_env_p, _c_void_p, _i64, _c_void_p, _c_void_p]),
+    "rtx_trace_lights_env": (_i32, [_c_void_p, _i32, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
+                                    _c_void_p, _i32, _c_void_p, _size, _c_void_p, _env_p]),
+    "rtx_trace_glass_env": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p, _i32,
+                                   _c_void_p, _size, _c_void_p, _env_p]),
 }
 
 _lib = None

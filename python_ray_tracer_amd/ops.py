@@ -66,6 +66,16 @@ that device's current HIP stream and returns a new tensor):
   allocates its own workspace. With ``check=True`` it reads the status word back (a synchronisation) and
   raises "maximum recursion depth exceeded" for a ray tree that overflowed a lane's stack of pending
   rays. Every tensor's dtype, device, contiguity and size is checked.
+* ``rt::env_sample(texels, gain, turn, dirs)``, ``rt::trace_lights_env(scene, n_spheres, lights, origins, dirs,
+  max_bounces, out_kind, texels, gain, turn, check=True)`` and ``rt::trace_glass_env(scene, n_spheres, glass,
+  origins, dirs, max_bounces, out_kind, texels, gain, turn, check=True)`` — the environment map (rtx_env_sample,
+  rtx_trace_lights_env, rtx_trace_glass_env; contract in include/rtx_hip.h): ``texels`` is the
+  device image float32 [H, W, 4] (RGB and a zero word: ``EnvironmentLight.texels``), at most 2^23 texels,
+  ``gain`` three finite numbers (intensity * colour), ``turn`` the rotation about +y in turns (degrees / 360).
+  ``env_sample`` returns env(D) of ``dirs`` float64 [3, n] as float64 [3, n]: the lookup alone. The other two
+  are ``rt::trace_lights`` / ``rt::trace_glass`` (same arguments, checks, workspace and ``check``) where a ray
+  that meets no shape returns env(D) instead of black, at every level; a blob of another sphere count (with
+  ``check=False``) makes every ray such a ray. Every tensor's dtype, device, contiguity and size is checked.
 * ``rt::edge_mask(color, id, hits, lit, width, height, contrast)``, ``rt::sample_dirs(sample_scene,
   k, width, height, pixels)`` and ``rt::resolve_scatter(samples, k, pixels, width, height, out,
   out_kind)`` — the three steps of adaptive anti-aliasing (HipRenderer(samples=k, adaptive=True);
@@ -112,7 +122,8 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "trace_lights", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
+       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "trace_lights", "env_sample",
+       "trace_lights_env", "trace_glass_env", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
        "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
        "comm_unique_id", "comm_init", "comm_destroy", "tiles_create", "tiles_submit", "tiles_finish",

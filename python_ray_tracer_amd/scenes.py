@@ -26,7 +26,9 @@ Spec layout::
      "lights": [{"kind": "point", "position": [x, y, z]},
                 (a point entry may also carry "intensity" and/or "color": [r, g, b]; either makes it a
                  domain.ColoredPointLight and the scene a multi-light scene, lights_spec)
-                {"kind": "dome", "intensity": i, "color": [r, g, b]}],
+                {"kind": "dome", "intensity": i, "color": [r, g, b]},
+                {"kind": "environment", "texels": (H, W, 3) colours, and, all optional, "intensity": i,
+                 "color": [r, g, b], "rotation": degrees}: a domain.EnvironmentLight, env_spec],
      "camera": {"position": [x, y, z], "width": W, "height": H}}
                 (with "target": [x, y, z] a domain.PerspectiveCamera; then also, all optional,
                  "up": [x, y, z], "fov": degrees, "lens_radius": r, "focus_distance": d)
@@ -116,6 +118,38 @@ def lights_spec(width: int = 1920, height: int = 1080) -> dict:
         {"kind": "point", "position": [-1.33, 8.16, 7.23], "intensity": 0.6, "color": [1.0, 0.7, 0.4]},
         {"kind": "point", "position": [0.18, 9.4, 3.89], "intensity": 0.4, "color": [0.4, 0.6, 1.0]},
     ]
+    return spec
+
+
+def sky_texels(width: int = 256, height: int = 128) -> np.ndarray:
+    """A procedural sky as an equirectangular float64 image (height, width, 3), so that nobody needs a
+    file: above the horizon a gradient from a pale horizon to a blue zenith, below it a darker ground,
+    and a sun disk of 5 degrees radius brighter than 1 (an HDR value) in the direction of the README
+    scene's light, (5, 10, -10). Row j, column i hold the colour of the direction at the texel's
+    centre: v = (j + 0.5) / height from the zenith down, u = (i + 0.5) / width about +y."""
+    w, h = int(width), int(height)
+    if w < 1 or h < 1:
+        raise ValueError(f"sky_texels: width and height must be >= 1, got {width} x {height}")
+    el = (0.5 - (np.arange(h) + 0.5) / h) * math.pi  # elevation of a row's centre
+    az = ((np.arange(w) + 0.5) / w - 0.5) * (2.0 * math.pi)  # atan2(z, x) of a column's centre
+    up = np.clip(np.sin(el), 0.0, 1.0)[:, None, None]
+    horizon, zenith, ground = np.array([0.85, 0.9, 1.0]), np.array([0.15, 0.35, 0.9]), np.array([0.2, 0.17, 0.14])
+    sky = horizon + (zenith - horizon) * np.sqrt(up)
+    img = np.where((el > 0.0)[:, None, None], sky, ground * (1.0 - 0.5 * np.clip(-np.sin(el), 0.0, 1.0)[:, None, None]))
+    img = np.broadcast_to(img, (h, w, 3)).copy()
+    sun = np.array([5.0, 10.0, -10.0]) / 15.0
+    d = np.stack([np.cos(el)[:, None] * np.cos(az)[None, :], np.broadcast_to(np.sin(el)[:, None], (h, w)),
+                  np.cos(el)[:, None] * np.sin(az)[None, :]], axis=-1)
+    img[(d @ sun) > math.cos(math.radians(5.0))] = [16.0, 14.0, 10.0]
+    return img
+
+
+def env_spec(width: int = 1920, height: int = 1080, env_width: int = 256, env_height: int = 128) -> dict:
+    """The README scene under the procedural sky (``sky_texels(env_width, env_height)``): every ray that
+    meets no sphere, reflected ones included, sees the sky. The environment frame of tools/env_bench.py,
+    the README and the tests (``rtx_trace_lights_env``)."""
+    spec = readme_spec(width, height)
+    spec["lights"].append({"kind": "environment", "texels": sky_texels(env_width, env_height)})
     return spec
 
 
@@ -213,7 +247,7 @@ CONFIGS = {
 
 def build_scene(spec: dict):
     """Instantiate ``spec`` with this package's HIP-backend classes."""
-    from python_ray_tracer_amd.domain import Camera, ColoredPointLight, DomeLight, PointLight, Scene3D
+    from python_ray_tracer_amd.domain import Camera, ColoredPointLight, DomeLight, EnvironmentLight, PointLight, Scene3D
     from python_ray_tracer_amd.infrastructure.hip import (
         HipRGBColor,
         HipShader,
@@ -248,6 +282,9 @@ def build_scene(spec: dict):
                                                 HipRGBColor(*li.get("color", (1.0, 1.0, 1.0)))))
             else:
                 lights.append(PointLight(HipVector3D(*li["position"])))
+        elif li["kind"] == "environment":  # an environment scene (env_spec)
+            lights.append(EnvironmentLight(li["texels"], li.get("intensity", 1.0),
+                                           HipRGBColor(*li.get("color", (1.0, 1.0, 1.0))), li.get("rotation", 0.0)))
         else:
             lights.append(DomeLight(li["intensity"], HipRGBColor(*li["color"])))
     cam = spec["camera"]
