@@ -747,6 +747,70 @@ int rtx_trace_glass_env(const double* scene, int n_spheres, const double* glass,
                         int out_kind, void* workspace, size_t workspace_bytes, void* stream,
                         const rtx_env_t* env);
 
+/* Triangle meshes (HipRenderer on a scene whose shapes hold a domain.TriangleMesh; the
+ * reference's Shape is an ABC with one subclass, the sphere, domain.py:43-50):
+ * NumpyRenderer.raytrace_scene (base.py:91-121) on n explicit rays through the spheres of `scene`
+ * (n_spheres may be 0) and the triangles of `mesh`, lit by the rows of `lights` as rtx_trace_lights
+ * lights its spheres (the same table, the same sums per hit).
+ * The triangle test is Möller–Trumbore, two-sided, float64 in this order exactly, no contraction, with
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ * a.x*b.y - a.y*b.x), and the triangle's v0, e1 = v1 - v0, e2 = v2 - v0 computed by the host:
+ *     T = O - v0;  P = cross(D, e2);  det = dot(e1, P);  f = 1.0 / det     (one division, correctly
+ *     u = f * dot(T, P);  Q = cross(T, e1);  v = f * dot(D, Q);  t = f * dot(e2, Q)          rounded)
+ *     hit  <=>  det != 0  and  u >= 0  and  v >= 0  and  u + v <= 1  and  0 < t  and  t < FARAWAY
+ * every comparison positive, so a NaN or an infinity from a tiny det is a miss; so are a ray in the
+ * triangle's plane (det == 0) and one that starts on it (t == 0).
+ * All triangles of a scene form one group, numbered in scene order, then face order (RTX_T_NUM). The
+ * group's hit is the triangle at the smallest t, the lowest number among equal t: triangles that
+ * share an edge or coincide never shade twice, and two coincident meshes do not add (unlike the
+ * reference's rule per Shape, base.py:97-103, which the spheres keep: every sphere at the nearest
+ * distance shades). If the group's t equals the spheres' nearest distance it shades too, after the
+ * spheres.
+ * For a triangle's hit at P = O + D*t (shader.py:73): N_g is the row's unit face normal, negated if
+ * dot(N_g, D) > 0 (it opposes the ray); the shading normal N is N_g for a flat row and, for a row with
+ * vertex normals, norm(((1 - u) - v)*n0 + u*n1 + v*n2) (u, v of the test above; each component (w*n0 +
+ * u*n1) + v*n2), negated if dot(N, N_g) < 0; the nudged point is Q = P + N_g*0.0001 (shader.py:77 with
+ * the face normal). Everything else of NumpyShader.create uses N as it uses a sphere's normal
+ * (diffuse, specular, iridescence, dome, the reflected direction), V towards the camera, the material
+ * the mesh's row; a checker reads P.x and P.z (shader.py:29-32).
+ * Shadows, per light, along L from Q, unbounded (the ray does not stop at the light, as in the
+ * reference): a sphere's hit is lit unless a sphere or a triangle is strictly nearer than the
+ * sphere's own distance t_self (shader.py:126-128 with the triangles taking part); a triangle's hit is
+ * lit unless any sphere or triangle, those of its own mesh included, has a hit along L (t_self =
+ * FARAWAY).
+ * `mesh` is the table of python_ray_tracer_amd.meshes.mesh_table, double [mesh_words]: a header of
+ * RTX_MESH_HDR_WORDS words (RTX_MH_*: the magic, the counts of triangles, meshes and nodes, the word
+ * offsets of the three parts, the table's length), the triangle rows (RTX_TRI_WORDS each, RTX_T_*) in
+ * the tree's leaf order, one material row (RTX_MAT_WORDS, RTX_M_*) per mesh, and the nodes of a
+ * bounding-volume tree over the triangles in depth-first order (RTX_NODE_WORDS, RTX_N_*: the box, a
+ * leaf's first row and count, the skip link, the margin the box is expanded by). The walk is stackless
+ * and wave-uniform: a node is entered when any lane may hit it before its nearest distance so far.
+ * A header whose magic, counts or offsets do not fit mesh_words means no triangles; a skip link that
+ * does not move forward is stepped over and a leaf's range is clamped to the rows, so no table makes
+ * the kernel read outside it or loop.
+ * Stacks, workspace (rtx_mesh_workspace_bytes), status word, out / out_kind, asynchrony and errors as
+ * rtx_trace_lights, with n_spheres in 0..RTX_MAX_SPHERES, max_bounces in 0..RTX_MESH_MAX_BOUNCES, and
+ * RTX_E_ARG also for a null mesh and for mesh_words below RTX_MESH_HDR_WORDS or above 2^31 - 1. */
+enum { RTX_MAX_TRIANGLES = 1 << 20, RTX_MESH_MAX_BOUNCES = 16, RTX_MESH_HDR_WORDS = 16, RTX_TRI_WORDS = 24 };
+#define RTX_MESH_MAGIC 1296388936.0
+enum { RTX_MH_MAGIC = 0, RTX_MH_NTRI, RTX_MH_NMESH, RTX_MH_NNODES, RTX_MH_TRIS, RTX_MH_MATS, RTX_MH_NODES, RTX_MH_WORDS };
+enum {
+  RTX_T_V0 = 0,      /* 3 words each: v0, e1, e2, the unit face normal */
+  RTX_T_E1 = 3,
+  RTX_T_E2 = 6,
+  RTX_T_NG = 9,
+  RTX_T_MESH = 12,   /* the mesh (its material row) */
+  RTX_T_SMOOTH = 13, /* 1: the row has vertex normals */
+  RTX_T_N0 = 14,     /* 3 words each: the normals at v0, v1, v2 */
+  RTX_T_N1 = 17,
+  RTX_T_N2 = 20,
+  RTX_T_NUM = 23     /* the triangle's number in the group */
+};
+size_t rtx_mesh_workspace_bytes(int64_t n_rays, int max_bounces);
+int rtx_trace_mesh(const double* scene, int n_spheres, const double* mesh, int64_t mesh_words, const double* lights,
+                   int n_lights, const double* origins, int64_t origin_stride, const double* dirs, int64_t n,
+                   int max_bounces, void* out, int out_kind, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts
  * gathered row tiles, part p at tiles + p * part_stride_bytes, each as rtx_render_camera wrote it

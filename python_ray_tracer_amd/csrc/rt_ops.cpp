@@ -21,6 +21,8 @@
 //                        through a scene with solid glass spheres (rtx_trace_glass); allocates its workspace
 //   rt::trace_lights  <- no counterpart (main.py, "TODO: use multiple lights"): raytrace_scene on explicit rays with
 //                        every point light of a table (rtx_trace_lights); allocates its workspace
+//   rt::trace_mesh    <- no counterpart (the reference's only Shape is the sphere): raytrace_scene on explicit rays
+//                        through the spheres and the triangles of a mesh table (rtx_trace_mesh)
 //   rt::env_sample, rt::trace_lights_env, rt::trace_glass_env
 //                     <- no counterpart (raytrace_scene adds nothing on a miss, base.py:100-121): the environment
 //                        map's lookup alone, and the two kernels above with it for every ray that meets no shape
@@ -821,6 +823,84 @@ at::Tensor trace_lights(const at::Tensor& scene, int64_t n_spheres, const at::Te
   return out;
 }
 
+// ---- triangle meshes (rtx_trace_mesh) -------------------------------------------------------------
+// Shapes and ranges of rt::trace_mesh's arguments, shared by the kernel and its Meta form: returns n.
+int64_t check_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                   const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind) {
+  TORCH_CHECK(scene.dim() == 1, "scene must be the 1-D packed blob (scene_pack.pack_scene)");
+  TORCH_CHECK(n_spheres >= 0 && n_spheres <= RTX_MAX_SPHERES, "n_spheres out of range: ", n_spheres);
+  TORCH_CHECK(scene.numel() >= RTX_HDR_WORDS + n_spheres * (RTX_GEOM_WORDS + RTX_MAT_WORDS),
+              "scene blob too short for ", n_spheres, " spheres");
+  TORCH_CHECK(mesh.scalar_type() == at::kDouble && mesh.dim() == 1 && mesh.numel() >= RTX_MESH_HDR_WORDS &&
+                  mesh.numel() <= INT32_MAX,
+              "mesh must be ", at::kDouble, " [words] with at least ", (int)RTX_MESH_HDR_WORDS,
+              " words (meshes.mesh_table), got ", mesh.scalar_type(), " ", mesh.sizes());
+  TORCH_CHECK(lights.scalar_type() == at::kDouble && lights.dim() == 2 && lights.size(1) == 6 &&
+                  lights.size(0) >= 1 && lights.size(0) <= RTX_MAX_POINT_LIGHTS,
+              "lights must be ", at::kDouble, " [L, 6] with L in 1..", (int)RTX_MAX_POINT_LIGHTS,
+              " (lights.lights_table), got ", lights.scalar_type(), " ", lights.sizes());
+  TORCH_CHECK(dirs.scalar_type() == at::kDouble && dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be ", at::kDouble,
+              " [3, n], got ", dirs.scalar_type(), " ", dirs.sizes());
+  const int64_t n = dirs.size(1);
+  TORCH_CHECK(origins.scalar_type() == at::kDouble &&
+                  ((origins.dim() == 1 && origins.numel() == 3) ||
+                   (origins.dim() == 2 && origins.size(0) == 3 && origins.size(1) == n)),
+              "origins must be ", at::kDouble, " [3] (shared) or [3, n] with n = ", n, ", got ", origins.scalar_type(),
+              " ", origins.sizes());
+  TORCH_CHECK(max_bounces >= 0 && max_bounces <= RTX_MESH_MAX_BOUNCES, "max_bounces must lie in 0..",
+              (int)RTX_MESH_MAX_BOUNCES, " (a mesh scene needs a finite cap), got ", max_bounces);
+  TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA || out_kind == RTX_OUT_U8_HWC,
+              "bad out_kind ", out_kind);
+  return n;
+}
+
+// The mesh table's header against its length: the host-side form of the kernel's own test, which reads a
+// table that fails it as one without triangles (one synchronous copy of the header)
+void check_mesh_header(const at::Tensor& mesh) {
+  const at::Tensor head = mesh.narrow(0, 0, RTX_MESH_HDR_WORDS).to(at::kCPU).contiguous();
+  const double* h = head.data_ptr<double>();
+  const double w = (double)mesh.numel(), T = h[RTX_MH_NTRI], M = h[RTX_MH_NMESH], N = h[RTX_MH_NNODES];
+  const double ta = h[RTX_MH_TRIS], ma = h[RTX_MH_MATS], na = h[RTX_MH_NODES];
+  TORCH_CHECK(h[RTX_MH_MAGIC] == RTX_MESH_MAGIC, "mesh is not a mesh table (bad magic; meshes.mesh_table)");
+  TORCH_CHECK(h[RTX_MH_WORDS] == w && T >= 1 && T <= RTX_MAX_TRIANGLES && M >= 1 && M <= T && N >= 1 && N <= 2 * T &&
+                  ta >= RTX_MESH_HDR_WORDS && ta + T * RTX_TRI_WORDS <= w && ma >= RTX_MESH_HDR_WORDS &&
+                  ma + M * RTX_MAT_WORDS <= w && na >= RTX_MESH_HDR_WORDS && na + N * RTX_NODE_WORDS <= w,
+              "mesh table: the header's counts and offsets do not fit its ", mesh.numel(), " words");
+}
+
+at::Tensor trace_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                      const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                      bool check) {
+  check_gpu(scene, "scene", at::kDouble);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  const struct { const at::Tensor& t; const char* name; } in[] = {
+      {mesh, "mesh"}, {lights, "lights"}, {origins, "origins"}, {dirs, "dirs"}};
+  for (const auto& a : in) {
+    check_gpu(a.t, a.name, at::kDouble);
+    check_same_device(scene, a.t, a.name);
+  }
+  const int64_t n = check_mesh(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind);
+  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
+  if (check) {
+    check_headers(scene, n_spheres);
+    check_mesh_header(mesh);
+  }
+  if (n == 0) return out;  // (an empty tensor's pointer may be null)
+  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
+  at::Tensor ws = at::zeros({(int64_t)rtx_mesh_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
+  check_rc(rtx_trace_mesh(scene.data_ptr<double>(), (int)n_spheres, mesh.data_ptr<double>(), mesh.numel(),
+                          lights.data_ptr<double>(), (int)lights.size(0), origins.data_ptr<double>(),
+                          origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n, (int)max_bounces, out.data_ptr(),
+                          (int)out_kind, ws.data_ptr(), (size_t)ws.numel(), stream_of(scene)),
+           "rtx_trace_mesh");
+  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
+    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
+    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
+                2 * max_bounces + 2, " pending rays; HipRenderer raises RecursionError)");
+  }
+  return out;
+}
+
 // ---- the environment map (rtx_env_sample, rtx_trace_lights_env, rtx_trace_glass_env) ----------------
 // Shapes and ranges of an environment's arguments, shared by the kernels and their Meta forms: texels
 // float32 [H, W, 4], gain three finite numbers, turn finite. Fills env but for its device pointer.
@@ -1122,6 +1202,13 @@ at::Tensor trace_lights_meta(const at::Tensor& scene, int64_t n_spheres, const a
   return new_output(scene, check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
 }
 
+at::Tensor trace_mesh_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                           const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                           bool) {
+  return new_output(scene, check_mesh(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind), -1, 0,
+                    out_kind);
+}
+
 at::Tensor env_sample_meta(const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, const at::Tensor& dirs) {
   rtx_env_t env;
   check_env(texels, gain, turn, env);
@@ -1205,6 +1292,8 @@ TORCH_LIBRARY(rt, m) {
         "int out_kind, bool check=True) -> Tensor");
   m.def("trace_lights(Tensor scene, int n_spheres, Tensor lights, Tensor origins, Tensor dirs, int max_bounces, "
         "int out_kind, bool check=True) -> Tensor");
+  m.def("trace_mesh(Tensor scene, int n_spheres, Tensor mesh, Tensor lights, Tensor origins, Tensor dirs, "
+        "int max_bounces, int out_kind, bool check=True) -> Tensor");
   m.def("env_sample(Tensor texels, float[] gain, float turn, Tensor dirs) -> Tensor");
   m.def("trace_lights_env(Tensor scene, int n_spheres, Tensor lights, Tensor origins, Tensor dirs, int max_bounces, "
         "int out_kind, Tensor texels, float[] gain, float turn, bool check=True) -> Tensor");
@@ -1245,6 +1334,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("occlusion", &occlusion);
   m.impl("trace_glass", &trace_glass);
   m.impl("trace_lights", &trace_lights);
+  m.impl("trace_mesh", &trace_mesh);
   m.impl("env_sample", &env_sample);
   m.impl("trace_lights_env", &trace_lights_env);
   m.impl("trace_glass_env", &trace_glass_env);
@@ -1271,6 +1361,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("occlusion", &occlusion);
   m.impl("trace_glass", &trace_glass);
   m.impl("trace_lights", &trace_lights);
+  m.impl("trace_mesh", &trace_mesh);
   m.impl("env_sample", &env_sample);
   m.impl("trace_lights_env", &trace_lights_env);
   m.impl("trace_glass_env", &trace_glass_env);
@@ -1295,6 +1386,7 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("occlusion", &occlusion_meta);
   m.impl("trace_glass", &trace_glass_meta);
   m.impl("trace_lights", &trace_lights_meta);
+  m.impl("trace_mesh", &trace_mesh_meta);
   m.impl("env_sample", &env_sample_meta);
   m.impl("trace_lights_env", &trace_lights_env_meta);
   m.impl("trace_glass_env", &trace_glass_env_meta);

@@ -314,12 +314,14 @@ def tile_gather_for(renderer, scene, *, group=None, row_block: int = 8, dst: int
     # a PerspectiveCamera's tile is generated rays traced by render_tile: the native plan (rtx_tiles_submit)
     # renders the reference camera, so such scenes take render_tile(into=) and the gather, like supersampling;
     # so does a multi-light scene, whose rays are traced by rtx_trace_lights (submit_tiles refuses it), and an
-    # environment scene (rtx_trace_lights_env / rtx_trace_glass_env)
+    # environment scene (rtx_trace_lights_env / rtx_trace_glass_env) and a mesh scene (rtx_trace_mesh)
     from python_ray_tracer_amd.camera import is_perspective
     from python_ray_tracer_amd.environment import environment_of
     from python_ray_tracer_amd.lights import is_multi_light
+    from python_ray_tracer_amd.meshes import is_mesh_scene
 
-    explicit = is_perspective(scene.camera) or is_multi_light(scene.lights) or environment_of(scene.lights) is not None
+    explicit = (is_perspective(scene.camera) or is_multi_light(scene.lights) or environment_of(scene.lights) is not None
+                or is_mesh_scene(scene.shapes))
     native = False if explicit else None
     key = (W, H, int(row_block), int(dst), "u8" if out == "u8" else None, id(group), dist.get_world_size(group),
            getattr(renderer, "color_dtype", None), native)

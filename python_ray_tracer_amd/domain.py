@@ -142,6 +142,47 @@ class Shape(ABC):
         pass
 
 
+class TriangleMesh(Shape):
+    """Triangles with one shader (no counterpart in the reference, whose only shape is the sphere:
+    ``Shape`` is an ABC with one subclass). One of them in ``scene.shapes`` makes the scene a mesh scene
+    (``python_ray_tracer_amd.meshes``, ``rtx_trace_mesh``).
+
+    ``vertices``: float [V, 3]. ``faces``: int [F, 3], indices into ``vertices``. ``normals``: float
+    [V, 3] for smooth shading (the shading normal is interpolated over a face), None for flat.
+    ``shader``: the material of every face, a ``HipShader`` (a plain or a checker texture; no image
+    texture, no transmission). The arrays are kept as float64 / int64 copies; they are validated where a
+    table is built from them (``meshes.mesh_table``)."""
+
+    def __init__(self, vertices, faces, shader, normals=None) -> None:
+        import numpy as np
+
+        self.vertices = np.array(vertices, dtype=np.float64)
+        self.faces = np.array(faces, dtype=np.int64)
+        self.shader = shader
+        self.normals = None if normals is None else np.array(normals, dtype=np.float64)
+
+    def intersect(self, ray_origin, normalized_ray_direction):
+        """The distance to the nearest triangle of this mesh (the two-sided Möller–Trumbore test of
+        include/rtx_hip.h, in NumPy, every face tried): float64, FARAWAY (1e39) where the ray misses."""
+        from python_ray_tracer_amd import meshes
+
+        return meshes.intersect_mesh(self, ray_origin, normalized_ray_direction)
+
+    def diffusecolor(self, intersection_point):
+        return self.shader.diffuse_color.get_color(intersection_point)
+
+    def placed(self, scale=1.0, translation=(0.0, 0.0, 0.0)) -> TriangleMesh:
+        """A copy with every vertex at ``vertex * scale + translation`` (``scale`` a number)."""
+        import numpy as np
+
+        v = self.vertices * float(scale) + np.asarray(translation, dtype=np.float64).reshape(1, 3)
+        return TriangleMesh(v, self.faces, self.shader, self.normals)
+
+    def __repr__(self) -> str:
+        return (f"TriangleMesh(<{len(self.vertices)} vertices, {len(self.faces)} faces, "
+                f"{'smooth' if self.normals is not None else 'flat'}>)")
+
+
 @dataclass
 class Scene3D:
     """Reference ``domain.py:53-59``."""

@@ -35,6 +35,8 @@ MAX_SAMPLES = 8  # samples per pixel side (rtx_resolve_samples)
 GLASS_MAX_BOUNCES = 8  # the largest bounce cap of a transmissive scene (rtx_trace_glass)
 MAX_POINT_LIGHTS = 8  # the rows of a multi-light scene's table (rtx_trace_lights)
 LIGHTS_MAX_BOUNCES = 16  # the largest bounce cap of a multi-light scene (rtx_trace_lights)
+MAX_TRIANGLES = 1 << 20  # the triangles of a mesh scene (rtx_trace_mesh)
+MESH_MAX_BOUNCES = 16  # the largest bounce cap of a mesh scene (rtx_trace_mesh)
 ENV_MAX_TEXELS = 1 << 23  # the largest environment image (rtx_env_t)
 MAGIC = 5527384.0
 UNBOUNDED = -1
@@ -125,6 +127,8 @@ EXPORTS = (
     "rtx_env_sample",
     "rtx_trace_lights_env",
     "rtx_trace_glass_env",
+    "rtx_mesh_workspace_bytes",
+    "rtx_trace_mesh",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -224,6 +228,9 @@ _SIGS = {
                                     _c_void_p, _i32, _c_void_p, _size, _c_void_p, _env_p]),
     "rtx_trace_glass_env": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p, _i32,
                                    _c_void_p, _size, _c_void_p, _env_p]),
+    "rtx_mesh_workspace_bytes": (_size, [_i64, _i32]),
+    "rtx_trace_mesh": (_i32, [_c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
+                              _c_void_p, _i32, _c_void_p, _size, _c_void_p]),
 }
 
 _lib = None

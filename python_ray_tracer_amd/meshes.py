@@ -1,0 +1,452 @@
+"""Host maths of triangle meshes (``rtx_trace_mesh``): the routing rule, an OBJ loader,
+a few generators, the triangle test in NumPy and the device table with its bounding-volume tree.
+
+A scene is a mesh scene if and only if ``scene.shapes`` holds at least one ``domain.TriangleMesh``.
+The triangles of every mesh form one group, numbered in scene order, then face order; the table holds
+them in the tree's leaf order, each with its number. Nothing here touches the GPU: a bad value raises
+ValueError before any device call.
+"""
+
+from __future__ import annotations
+
+import hashlib
+
+import numpy as np
+
+from python_ray_tracer_amd.domain import TriangleMesh
+
+FARAWAY = 1.0e39
+MAX_TRIANGLES = 1 << 20  # RTX_MAX_TRIANGLES
+MAX_BOUNCES = 16  # RTX_MESH_MAX_BOUNCES
+MAGIC = 1296388936.0  # RTX_MESH_MAGIC
+HDR_WORDS = 16  # RTX_MESH_HDR_WORDS
+# header words (RTX_MH_*)
+MH_MAGIC, MH_NTRI, MH_NMESH, MH_NNODES, MH_TRIS, MH_MATS, MH_NODES, MH_WORDS = range(8)
+TRI_WORDS = 24  # RTX_TRI_WORDS
+# triangle row words (RTX_T_*): v0, e1 = v1 - v0, e2 = v2 - v0, the unit face normal, the mesh, 1 for
+# vertex normals, the three vertex normals, the triangle's number in the group
+T_V0, T_E1, T_E2, T_NG, T_MESH, T_SMOOTH, T_N0, T_N1, T_N2, T_NUM = 0, 3, 6, 9, 12, 13, 14, 17, 20, 23
+MARGIN = 2e-7  # a node's margin is MARGIN * (1 + the largest |corner|^2), DESIGN.md §17
+
+
+def is_mesh_scene(shapes) -> bool:
+    """Whether ``shapes`` holds a ``TriangleMesh`` (nothing is validated)."""
+    return any(isinstance(sh, TriangleMesh) for sh in shapes)
+
+
+def check_bounces(max_bounces) -> int:
+    """The bounce cap of a mesh render: an int in 0..MAX_BOUNCES. ValueError for None (the kernel keeps
+    a lane's pending rays in a stack sized by the cap) and for a larger cap."""
+    if max_bounces is None:
+        raise ValueError("a scene with a TriangleMesh needs a finite bounce cap: "
+                         f"HipRenderer(max_bounces=B) with B in 0..{MAX_BOUNCES}")
+    if isinstance(max_bounces, bool) or int(max_bounces) != max_bounces or not 0 <= max_bounces <= MAX_BOUNCES:
+        raise ValueError(f"a scene with a TriangleMesh renders with HipRenderer(max_bounces=B), B in "
+                         f"0..{MAX_BOUNCES}, got {max_bounces!r}")
+    return int(max_bounces)
+
+
+# ---------------------------------------------------------------------------------------------
+# the triangle test
+# ---------------------------------------------------------------------------------------------
+def _dot(ax, ay, az, bx, by, bz):
+    return (ax * bx + ay * by) + az * bz
+
+
+def intersect_triangles(v0, e1, e2, ox, oy, oz, dx, dy, dz):
+    """The two-sided Möller–Trumbore test of include/rtx_hip.h for triangles [F] (``v0``, ``e1``, ``e2``
+    float64 [F, 3]) against rays [n]: (t, u, v) float64 [F, n], t FARAWAY where the ray misses."""
+    ox, oy, oz, dx, dy, dz = (np.asarray(a, dtype=np.float64).reshape(1, -1) for a in (ox, oy, oz, dx, dy, dz))
+    c = [np.ascontiguousarray(a[:, i]).reshape(-1, 1) for a in (v0, e1, e2) for i in range(3)]
+    v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z = c
+    with np.errstate(all="ignore"):
+        tx, ty, tz = ox - v0x, oy - v0y, oz - v0z
+        px, py, pz = dy * e2z - dz * e2y, dz * e2x - dx * e2z, dx * e2y - dy * e2x
+        det = _dot(e1x, e1y, e1z, px, py, pz)
+        f = 1.0 / det
+        u = f * _dot(tx, ty, tz, px, py, pz)
+        qx, qy, qz = ty * e1z - tz * e1y, tz * e1x - tx * e1z, tx * e1y - ty * e1x
+        v = f * _dot(dx, dy, dz, qx, qy, qz)
+        t = f * _dot(e2x, e2y, e2z, qx, qy, qz)
+        hit = (det != 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t > 0) & (t < FARAWAY)
+    return np.where(hit, t, FARAWAY), u, v
+
+
+def intersect_mesh(mesh, ray_origin, ray_direction):
+    """``TriangleMesh.intersect``: the smallest t over the mesh's faces per ray (FARAWAY: a miss)."""
+    v, f = mesh.vertices, mesh.faces
+    v0 = v[f[:, 0]]
+    d = [np.atleast_1d(np.asarray(c, dtype=np.float64)) for c in _components(ray_direction)]
+    n = max(a.size for a in d)
+    o = [np.broadcast_to(np.asarray(c, dtype=np.float64), (n,)) for c in _components(ray_origin)]
+    d = [np.broadcast_to(a, (n,)) for a in d]
+    best = np.full(n, FARAWAY)
+    for k in range(0, len(f), 4096):  # (blocks: the [F, n] intermediates stay small)
+        s = slice(k, k + 4096)
+        t, _, _ = intersect_triangles(v0[s], v[f[s, 1]] - v0[s], v[f[s, 2]] - v0[s], *o, *d)
+        best = np.minimum(best, t.min(axis=0))
+    return best
+
+
+def _components(v):
+    return v.components() if hasattr(v, "components") else tuple(v)
+
+
+# ---------------------------------------------------------------------------------------------
+# OBJ files and generators
+# ---------------------------------------------------------------------------------------------
+def vertex_normals(vertices, faces) -> np.ndarray:
+    """Area-weighted vertex normals [V, 3]: the sum of the faces' (unnormalised) cross products at each
+    vertex, normalised (a vertex of no face, or whose faces cancel: the zero vector)."""
+    v = np.asarray(vertices, dtype=np.float64)
+    f = np.asarray(faces, dtype=np.int64)
+    fn = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    out = np.zeros_like(v)
+    for i in range(3):
+        np.add.at(out, f[:, i], fn)
+    mag = np.sqrt((out * out).sum(axis=1, keepdims=True))
+    return out / np.where(mag == 0, 1.0, mag)
+
+
+def load_obj(path, shader, smooth: bool = False) -> TriangleMesh:
+    """The mesh of a Wavefront OBJ file: ``v`` and ``vn`` records, ``f`` records with ``v``, ``v/vt``,
+    ``v//vn`` and ``v/vt/vn`` indices (1-based, or negative: counted back from the latest record),
+    polygons fan-triangulated from their first corner; comments and every other record are ignored.
+    ``smooth``: with vertex normals, the file's ``vn`` where every corner names one (a vertex that
+    several corners give different normals is split), else area-weighted ones (``vertex_normals``).
+    ValueError for a record that does not parse and for an index out of range."""
+    verts, norms, corners, faces = [], [], {}, []
+    out_v, out_n = [], []
+    any_vn, all_vn = False, True
+
+    def index(tok: str, count: int, what: str, line_no: int) -> int:
+        try:
+            i = int(tok)
+        except ValueError:
+            raise ValueError(f"{path}:{line_no}: bad {what} index {tok!r}") from None
+        j = i - 1 if i > 0 else count + i
+        if i == 0 or not 0 <= j < count:
+            raise ValueError(f"{path}:{line_no}: {what} index {i} out of range (1..{count})")
+        return j
+
+    with open(path, encoding="utf-8", errors="replace") as fh:
+        for line_no, line in enumerate(fh, 1):
+            parts = line.split("#", 1)[0].split()
+            if not parts:
+                continue
+            if parts[0] in ("v", "vn"):
+                try:
+                    xyz = [float(x) for x in parts[1:4]]
+                except ValueError:
+                    raise ValueError(f"{path}:{line_no}: bad {parts[0]} record") from None
+                if len(xyz) != 3:
+                    raise ValueError(f"{path}:{line_no}: a {parts[0]} record needs three numbers")
+                (verts if parts[0] == "v" else norms).append(xyz)
+            elif parts[0] == "f":
+                if len(parts) < 4:
+                    raise ValueError(f"{path}:{line_no}: a face needs at least three corners")
+                poly = []
+                for tok in parts[1:]:
+                    fields = tok.split("/")
+                    vi = index(fields[0], len(verts), "vertex", line_no)
+                    ni = None
+                    if len(fields) >= 3 and fields[2] != "":
+                        ni = index(fields[2], len(norms), "normal", line_no)
+                        any_vn = True
+                    else:
+                        all_vn = False
+                    key = (vi, ni)
+                    if key not in corners:
+                        corners[key] = len(out_v)
+                        out_v.append(verts[vi])
+                        out_n.append(norms[ni] if ni is not None else (0.0, 0.0, 0.0))
+                    poly.append(corners[key])
+                faces += [(poly[0], poly[i], poly[i + 1]) for i in range(1, len(poly) - 1)]
+    use_vn = smooth and any_vn and all_vn
+    if not use_vn:  # the file's vertices in the file's order: corners that differ in their normal alone are one
+        remap = np.zeros(len(out_v), dtype=np.int64)
+        for (vi, _ni), k in corners.items():
+            remap[k] = vi
+        out_v = verts
+        faces = remap[np.asarray(faces, dtype=np.int64).reshape(-1, 3)]
+    v = np.asarray(out_v, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    normals = None
+    if use_vn:
+        normals = np.asarray(out_n, dtype=np.float64).reshape(-1, 3)
+    elif smooth:
+        normals = vertex_normals(v, f)
+    return TriangleMesh(v, f, shader, normals)
+
+
+def quad(corners, shader) -> TriangleMesh:
+    """Two triangles (0, 1, 2) and (0, 2, 3) over four corners given in order round the quad."""
+    c = np.asarray(corners, dtype=np.float64).reshape(4, 3)
+    return TriangleMesh(c, [(0, 1, 2), (0, 2, 3)], shader)
+
+
+def box(lo, hi, shader) -> TriangleMesh:
+    """The axis-aligned box from ``lo`` to ``hi``: 8 vertices, 12 triangles, normals outwards."""
+    (x0, y0, z0), (x1, y1, z1) = (tuple(float(x) for x in lo), tuple(float(x) for x in hi))
+    v = [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)]
+    q = [(0, 3, 2, 1), (4, 5, 6, 7), (0, 1, 5, 4), (2, 3, 7, 6), (1, 2, 6, 5), (0, 4, 7, 3)]
+    f = [t for a, b, c, d in q for t in ((a, b, c), (a, c, d))]
+    return TriangleMesh(v, f, shader)
+
+
+def icosphere(level: int, shader, smooth: bool = False) -> TriangleMesh:
+    """The unit sphere about the origin as an icosahedron subdivided ``level`` times (each triangle
+    into four, the new vertices pushed onto the sphere): 20 * 4**level triangles. ``smooth``: the
+    vertex normals are the vertices themselves."""
+    if isinstance(level, bool) or int(level) != level or not 0 <= level <= 7:
+        raise ValueError(f"icosphere: level must be an int in 0..7, got {level!r}")
+    p = (1.0 + 5.0 ** 0.5) / 2.0
+    v = np.array([(-1, p, 0), (1, p, 0), (-1, -p, 0), (1, -p, 0), (0, -1, p), (0, 1, p), (0, -1, -p), (0, 1, -p),
+                  (p, 0, -1), (p, 0, 1), (-p, 0, -1), (-p, 0, 1)], dtype=np.float64)
+    f = np.array([(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2),
+                  (10, 7, 6), (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11),
+                  (6, 2, 10), (8, 6, 7), (9, 8, 1)], dtype=np.int64)
+    v /= np.sqrt((v * v).sum(axis=1, keepdims=True))
+    for _ in range(int(level)):
+        nv = len(v)
+        edges = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)
+        uniq, inv = np.unique(edges, axis=0, return_inverse=True)
+        mid = v[uniq[:, 0]] + v[uniq[:, 1]]
+        mid /= np.sqrt((mid * mid).sum(axis=1, keepdims=True))
+        v = np.concatenate([v, mid])
+        m = nv + inv.reshape(3, -1)  # the midpoints of edges (0,1), (1,2), (2,0) per face
+        a, b, c = f[:, 0], f[:, 1], f[:, 2]
+        f = np.concatenate([np.stack([a, m[0], m[2]], 1), np.stack([b, m[1], m[0]], 1),
+                            np.stack([c, m[2], m[1]], 1), np.stack([m[0], m[1], m[2]], 1)])
+    return TriangleMesh(v, f, shader, v.copy() if smooth else None)
+
+
+def torus(R: float, r: float, nu: int, nv: int, shader, smooth: bool = False) -> TriangleMesh:
+    """A torus about the y axis through the origin: ``R`` the radius of the tube's centre circle, ``r``
+    the tube's, ``nu`` segments round the axis and ``nv`` round the tube: 2 * nu * nv triangles.
+    ``smooth``: the vertex normals point from the tube's centre circle."""
+    if int(nu) != nu or int(nv) != nv or nu < 3 or nv < 3:
+        raise ValueError(f"torus: nu and nv must be ints >= 3, got {nu!r} and {nv!r}")
+    nu, nv = int(nu), int(nv)
+    a = (np.arange(nu) * (2.0 * np.pi / nu)).reshape(-1, 1)
+    b = (np.arange(nv) * (2.0 * np.pi / nv)).reshape(1, -1)
+    n = np.stack([np.cos(b) * np.cos(a), np.sin(b) * np.ones_like(a), np.cos(b) * np.sin(a)], axis=-1).reshape(-1, 3)
+    centre = np.stack([np.cos(a) * np.ones_like(b), np.zeros((nu, nv)), np.sin(a) * np.ones_like(b)], axis=-1)
+    v = float(R) * centre.reshape(-1, 3) + float(r) * n
+    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    i1, j1 = (i + 1) % nu, (j + 1) % nv
+    p00, p10, p11, p01 = (i * nv + j).ravel(), (i1 * nv + j).ravel(), (i1 * nv + j1).ravel(), (i * nv + j1).ravel()
+    f = np.concatenate([np.stack([p00, p11, p10], 1), np.stack([p00, p01, p11], 1)])
+    return TriangleMesh(v, f, shader, n if smooth else None)
+
+
+# ---------------------------------------------------------------------------------------------
+# the device table
+# ---------------------------------------------------------------------------------------------
+def _mesh_arrays(mesh, i: int):
+    """(vertices [V, 3], faces [F, 3], normals or None) of mesh ``i``, validated."""
+    v = np.asarray(mesh.vertices, dtype=np.float64)
+    f = np.asarray(mesh.faces)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"mesh {i}: vertices must be [V, 3], got {v.shape}")
+    if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"mesh {i}: faces must be int [F, 3], got {f.dtype} {f.shape}")
+    if f.shape[0] == 0:
+        raise ValueError(f"mesh {i}: no faces")
+    if not np.isfinite(v).all():
+        raise ValueError(f"mesh {i}: a vertex is not finite")
+    if f.min() < 0 or f.max() >= v.shape[0]:
+        raise ValueError(f"mesh {i}: a face index lies outside 0..{v.shape[0] - 1}")
+    n = mesh.normals
+    if n is not None:
+        n = np.asarray(n, dtype=np.float64)
+        if n.shape != v.shape:
+            raise ValueError(f"mesh {i}: normals must be [V, 3] like the vertices {v.shape}, got {n.shape}")
+        if not np.isfinite(n).all():
+            raise ValueError(f"mesh {i}: a vertex normal is not finite")
+    return v, f.astype(np.int64), n
+
+
+def _mesh_material(mesh, i: int) -> list:
+    """The material row of mesh ``i``'s shader (the spheres' record, scene_pack._material_row)."""
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+    from python_ray_tracer_amd.infrastructure.hip.scene_pack import _material_row
+
+    sh = mesh.shader
+    tex = sh.diffuse_color
+    if getattr(sh, "transmission_gain", 0.0):
+        raise ValueError(f"mesh {i}: transmission_gain != 0; there is no refraction through a mesh")
+    if type(tex).__name__ == "TextureChecker":
+        tex_fields = (L.TEX_CHECKER, 1.0, 1.0, 1.0)
+    elif hasattr(tex, "texels"):
+        raise ValueError(f"mesh {i}: an ImageTexture needs texture coordinates, which a mesh does not have")
+    elif hasattr(tex, "color"):
+        tex_fields = (L.TEX_CONST, float(tex.color.x), float(tex.color.y), float(tex.color.z))
+    else:
+        raise ValueError(f"mesh {i}: unsupported texture {type(tex).__name__}")
+    return _material_row((None, None, tex_fields, sh.specular_gain, sh.diffuse_gain, sh.specular_roughness,
+                          sh.specular_ior, sh.iridescence_gain, sh.thin_film_weight, sh.thin_film_thickness,
+                          sh.thin_film_ior, sh.reflection_gain))
+
+
+def triangle_rows(shapes):
+    """(rows float64 [T, TRI_WORDS] in group order, material rows [M, MAT_WORDS]) of the meshes of
+    ``shapes``, validated. ValueError as ``mesh_table``."""
+    rows, mats, base = [], [], 0
+    meshes = [sh for sh in shapes if isinstance(sh, TriangleMesh)]
+    if not meshes:
+        raise ValueError("no TriangleMesh among the shapes")
+    for i, mesh in enumerate(meshes):
+        v, f, n = _mesh_arrays(mesh, i)
+        mats.append(_mesh_material(mesh, i))
+        F = f.shape[0]
+        if base + F > MAX_TRIANGLES:
+            raise ValueError(f"at most {MAX_TRIANGLES} triangles per scene (RTX_MAX_TRIANGLES), got more")
+        v0 = v[f[:, 0]]
+        e1, e2 = v[f[:, 1]] - v0, v[f[:, 2]] - v0
+        ng = np.cross(e1, e2)
+        with np.errstate(all="ignore"):
+            ng = ng / np.sqrt((ng * ng).sum(axis=1, keepdims=True))
+        bad = ~np.isfinite(ng).all(axis=1)
+        if bad.any():
+            raise ValueError(f"mesh {i}: face {int(np.nonzero(bad)[0][0])} is degenerate (its normal cannot be "
+                             "normalised)")
+        r = np.zeros((F, TRI_WORDS))
+        r[:, T_V0:T_V0 + 3], r[:, T_E1:T_E1 + 3], r[:, T_E2:T_E2 + 3], r[:, T_NG:T_NG + 3] = v0, e1, e2, ng
+        r[:, T_MESH] = i
+        if n is not None:
+            r[:, T_SMOOTH] = 1.0
+            r[:, T_N0:T_N0 + 3], r[:, T_N1:T_N1 + 3], r[:, T_N2:T_N2 + 3] = n[f[:, 0]], n[f[:, 1]], n[f[:, 2]]
+        r[:, T_NUM] = base + np.arange(F)
+        rows.append(r)
+        base += F
+    return np.concatenate(rows), np.asarray(mats, dtype=np.float64).reshape(len(mats), -1)
+
+
+def build_tree(lo, hi, max_leaf):
+    """A bounding-volume tree over boxes (``lo``, ``hi`` float64 [T, 3]), built level by level: every
+    segment of more than ``max_leaf`` boxes (None: one leaf holds them all) is sorted by its boxes'
+    centres along the longest axis of the centres' extent and cut at the median. Returns (order [T]:
+    the boxes in leaf order, starts, ends [N]: every node's range of ``order`` in depth-first order)."""
+    T = lo.shape[0]
+    centre = (lo + hi) * 0.5
+    order = np.arange(T)
+    starts, ends = [np.array([0])], [np.array([T])]
+    s, e = starts[0], ends[0]
+    leaf = T if max_leaf is None else int(max_leaf)
+    while True:
+        big = (e - s) > leaf
+        s, e = s[big], e[big]
+        if s.size == 0:
+            break
+        # the triangles of the segments to cut, with their segment's number
+        length = e - s
+        seg = np.repeat(np.arange(s.size), length)
+        pos = np.arange(length.sum()) - np.repeat(np.cumsum(length) - length, length) + np.repeat(s, length)
+        c = centre[order[pos]]
+        first = np.cumsum(length) - length
+        ext = np.maximum.reduceat(c, first, axis=0) - np.minimum.reduceat(c, first, axis=0)
+        axis = np.argmax(ext, axis=1)
+        key = c[np.arange(c.shape[0]), axis[seg]]
+        by = np.lexsort((order[pos], key, seg))  # (the triangle's index last: a total order)
+        order[pos] = order[pos][by]
+        mid = s + (length + 1) // 2
+        s, e = np.concatenate([s, mid]), np.concatenate([mid, e])
+        starts.append(s)
+        ends.append(e)
+    s, e = np.concatenate(starts), np.concatenate(ends)
+    dfs = np.lexsort((-(e - s), s))  # depth first: by start, a parent before its first child
+    return order, s[dfs], e[dfs]
+
+
+def _content_digest(shapes) -> str:
+    """The digest of everything a table is built from: every mesh's arrays and material row."""
+    h = hashlib.blake2b(digest_size=16)
+    k = 0
+    for sh in shapes:
+        if not isinstance(sh, TriangleMesh):
+            continue
+        h.update(np.asarray(_mesh_material(sh, k), dtype=np.float64).tobytes())
+        for a in (sh.vertices, sh.faces, sh.normals):
+            a = np.ascontiguousarray(np.zeros(0) if a is None else a)
+            h.update(repr((a.dtype.str, a.shape)).encode())
+            h.update(a.tobytes())
+        k += 1
+    return h.hexdigest()
+
+
+def mesh_table(shapes, max_leaf=4) -> np.ndarray:
+    """The float64 table of ``rtx_trace_mesh`` for the meshes of ``shapes`` (layout in
+    include/rtx_hip.h): a header, the triangle rows in the tree's leaf order, one material row per mesh
+    and the tree's nodes in depth-first order with skip links, in the culling tree's node shape (box,
+    first, count, skip, margin). ``max_leaf``: the most triangles of a leaf (None: one leaf). Cached by
+    content. ValueError for vertices that are not finite, face indices out of range, a mesh without
+    faces, a degenerate face (one whose normal cannot be normalised; none is dropped), normals of the
+    wrong shape, an image texture or a transmissive shader on a mesh, and more than MAX_TRIANGLES
+    triangles."""
+    return mesh_table_entry(shapes, max_leaf)[0]
+
+
+def mesh_table_entry(shapes, max_leaf=4) -> tuple:
+    """(``mesh_table``, its content key): the key names the meshes' content and ``max_leaf``."""
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+
+    if max_leaf is not None and (isinstance(max_leaf, bool) or int(max_leaf) != max_leaf or max_leaf < 1):
+        raise ValueError(f"max_leaf must be None or an int >= 1, got {max_leaf!r}")
+    shapes = list(shapes)
+    key = (_content_digest(shapes), max_leaf)
+    hit = _TABLES.get(key)
+    if hit is not None:
+        return hit, key
+    rows, mats = triangle_rows(shapes)
+    v0, e1, e2 = rows[:, T_V0:T_V0 + 3], rows[:, T_E1:T_E1 + 3], rows[:, T_E2:T_E2 + 3]
+    corners = np.stack([v0, v0 + e1, v0 + e2])
+    lo, hi = corners.min(axis=0), corners.max(axis=0)
+    order, s, e = build_tree(lo, hi, max_leaf)
+    lo, hi = lo[order], hi[order]
+    T, N = rows.shape[0], s.shape[0]
+    # every node's box: reduceat over (start, end) pairs, a sentinel row for end == T
+    pairs = np.stack([s, e], axis=1).ravel()
+    nlo = np.minimum.reduceat(np.concatenate([lo, lo[-1:]]), pairs, axis=0)[::2]
+    nhi = np.maximum.reduceat(np.concatenate([hi, hi[-1:]]), pairs, axis=0)[::2]
+    nodes = np.zeros((N, L.NODE_WORDS))
+    nodes[:, L.N_LOX:L.N_LOX + 3], nodes[:, L.N_HIX:L.N_HIX + 3] = nlo, nhi
+    inner = np.zeros(N, dtype=bool)
+    inner[:-1] = s[1:] == s[:-1]  # a node followed by one of the same start has children
+    nodes[:, L.N_FIRST] = s
+    nodes[:, L.N_COUNT] = np.where(inner, 0, e - s)
+    nodes[:, L.N_SKIP] = np.searchsorted(s, e, side="left")  # the first node at or after the range's end
+    far = (np.maximum(np.abs(nlo), np.abs(nhi)) ** 2).sum(axis=1)  # the largest |corner|^2
+    nodes[:, L.N_MARGIN] = MARGIN * (1.0 + far)
+    head = np.zeros(HDR_WORDS)
+    tris_at = HDR_WORDS
+    mats_at = tris_at + T * TRI_WORDS
+    nodes_at = mats_at + mats.size
+    words = nodes_at + nodes.size
+    head[[MH_MAGIC, MH_NTRI, MH_NMESH, MH_NNODES, MH_TRIS, MH_MATS, MH_NODES, MH_WORDS]] = (
+        MAGIC, T, mats.shape[0], N, tris_at, mats_at, nodes_at, words)
+    table = np.concatenate([head, rows[order].ravel(), mats.ravel(), nodes.ravel()])
+    table.setflags(write=False)
+    if len(_TABLES) >= 8:
+        _TABLES.pop(next(iter(_TABLES)))
+    _TABLES[key] = table
+    return table, key
+
+
+_TABLES: dict = {}  # (content digest, max_leaf) -> table
+
+
+def check_table(table) -> None:
+    """ValueError unless ``table``'s header is that of a mesh table of its own length: the magic, the
+    counts and the three parts within it (what rtx_trace_mesh's kernel checks before it reads them)."""
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+
+    t = np.asarray(table)
+    if t.dtype != np.float64 or t.ndim != 1 or t.size < HDR_WORDS or t[MH_MAGIC] != MAGIC:
+        raise ValueError("not a mesh table (meshes.mesh_table): float64 [words] with the mesh magic")
+    T, M, N, a, b, c, w = (int(x) for x in t[[MH_NTRI, MH_NMESH, MH_NNODES, MH_TRIS, MH_MATS, MH_NODES, MH_WORDS]])
+    ok = (1 <= T <= MAX_TRIANGLES and 1 <= M <= T and 1 <= N <= 2 * T and w == t.size and a >= HDR_WORDS
+          and a + T * TRI_WORDS <= w and b >= HDR_WORDS and b + M * L.MAT_WORDS <= w and c >= HDR_WORDS
+          and c + N * L.NODE_WORDS <= w)
+    if not ok:
+        raise ValueError("mesh table: the header's counts and offsets do not fit the table")

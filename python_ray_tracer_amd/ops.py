@@ -66,6 +66,13 @@ that device's current HIP stream and returns a new tensor):
   allocates its own workspace. With ``check=True`` it reads the status word back (a synchronisation) and
   raises "maximum recursion depth exceeded" for a ray tree that overflowed a lane's stack of pending
   rays. Every tensor's dtype, device, contiguity and size is checked.
+* ``rt::trace_mesh(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check=True)`` —
+  raytrace_scene on explicit rays through the spheres of ``scene`` (``n_spheres`` may be 0) and the triangles
+  of ``mesh`` (rtx_trace_mesh; contract in include/rtx_hip.h): ``mesh`` is the device table
+  float64 [words] of ``meshes.mesh_table``, ``lights`` the table float64 [L, 6] of ``rt::trace_lights``,
+  ``max_bounces`` in 0..16; origins, out_kind, workspace and ``check`` as ``rt::trace_lights``. With
+  ``check=True`` the mesh table's header is read back and checked against its length too. Every tensor's
+  dtype, device, contiguity and size is checked.
 * ``rt::env_sample(texels, gain, turn, dirs)``, ``rt::trace_lights_env(scene, n_spheres, lights, origins, dirs,
   max_bounces, out_kind, texels, gain, turn, check=True)`` and ``rt::trace_glass_env(scene, n_spheres, glass,
   origins, dirs, max_bounces, out_kind, texels, gain, turn, check=True)`` — the environment map (rtx_env_sample,
@@ -122,7 +129,8 @@ from python_ray_tracer_amd.infrastructure.hip import _lib
 OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
-       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "trace_lights", "env_sample",
+       "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "trace_lights", "trace_mesh",
+       "env_sample",
        "trace_lights_env", "trace_glass_env", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
        "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)

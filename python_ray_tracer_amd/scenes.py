@@ -29,6 +29,12 @@ Spec layout::
                 {"kind": "dome", "intensity": i, "color": [r, g, b]},
                 {"kind": "environment", "texels": (H, W, 3) colours, and, all optional, "intensity": i,
                  "color": [r, g, b], "rotation": degrees}: a domain.EnvironmentLight, env_spec],
+     "meshes": [...] (optional: domain.TriangleMesh shapes after the spheres, a mesh scene, mesh_spec; each
+                {"kind": "quad", "corners": four points} | {"kind": "box", "lo": .., "hi": ..} |
+                {"kind": "icosphere", "level": n} | {"kind": "torus", "R": .., "r": .., "nu": .., "nv": ..} |
+                {"kind": "triangles", "vertices": [V, 3], "faces": [F, 3], and optionally "normals": [V, 3]},
+                with "shader" as a sphere's and, all optional, "smooth": bool, "scale": s,
+                "translation": [x, y, z])
      "camera": {"position": [x, y, z], "width": W, "height": H}}
                 (with "target": [x, y, z] a domain.PerspectiveCamera; then also, all optional,
                  "up": [x, y, z], "fov": degrees, "lens_radius": r, "focus_distance": d)
@@ -119,6 +125,48 @@ def lights_spec(width: int = 1920, height: int = 1080) -> dict:
         {"kind": "point", "position": [0.18, 9.4, 3.89], "intensity": 0.4, "color": [0.4, 0.6, 1.0]},
     ]
     return spec
+
+
+def mesh_spec(width: int = 1920, height: int = 1080, level: int = 2) -> dict:
+    """The README scene with its ground sphere replaced by a checkered quad, and a smooth icosphere
+    (``level`` subdivisions: 20 * 4**level triangles) and a torus added: the mesh frame of
+    tools/mesh_bench.py, the README and the tests (``rtx_trace_mesh``)."""
+    spec = readme_spec(width, height)
+    ground = spec["spheres"].pop(2)
+    gains = (0.8, 1.0, 0.5, 0.05, 1.0)
+    spec["meshes"] = [
+        {"kind": "quad", "corners": [[-40, -0.5, -10], [-40, -0.5, 60], [40, -0.5, 60], [40, -0.5, -10]],
+         "shader": ground["shader"]},
+        {"kind": "icosphere", "level": int(level), "smooth": True, "scale": 0.45, "translation": [-1.5, -0.05, 1.75],
+         "shader": _shader(*gains, _const(0.2, 0.6, 1.0))},
+        {"kind": "torus", "R": 0.5, "r": 0.17, "nu": 32, "nv": 16, "smooth": True, "translation": [0.7, -0.33, 0.9],
+         "shader": _shader(*gains, _const(1.0, 0.6, 0.1))},
+    ]
+    return spec
+
+
+def mesh_arrays(m: dict):
+    """(vertices [V, 3], faces [F, 3], normals [V, 3] or None) of one entry of a spec's "meshes", placed
+    by its "scale" and "translation"."""
+    from python_ray_tracer_amd import meshes
+
+    kind, smooth = m["kind"], bool(m.get("smooth", False))
+    if kind == "quad":
+        mesh = meshes.quad(m["corners"], None)
+    elif kind == "box":
+        mesh = meshes.box(m["lo"], m["hi"], None)
+    elif kind == "icosphere":
+        mesh = meshes.icosphere(m["level"], None, smooth)
+    elif kind == "torus":
+        mesh = meshes.torus(m["R"], m["r"], m["nu"], m["nv"], None, smooth)
+    elif kind == "triangles":
+        mesh = meshes.TriangleMesh(m["vertices"], m["faces"], None, m.get("normals"))
+    else:
+        raise ValueError(f"unknown mesh kind {kind!r}")
+    if smooth and mesh.normals is None:
+        mesh.normals = meshes.vertex_normals(mesh.vertices, mesh.faces)
+    mesh = mesh.placed(m.get("scale", 1.0), m.get("translation", (0.0, 0.0, 0.0)))
+    return mesh.vertices, mesh.faces, mesh.normals
 
 
 def sky_texels(width: int = 256, height: int = 128) -> np.ndarray:
@@ -247,7 +295,8 @@ CONFIGS = {
 
 def build_scene(spec: dict):
     """Instantiate ``spec`` with this package's HIP-backend classes."""
-    from python_ray_tracer_amd.domain import Camera, ColoredPointLight, DomeLight, EnvironmentLight, PointLight, Scene3D
+    from python_ray_tracer_amd.domain import (Camera, ColoredPointLight, DomeLight, EnvironmentLight, PointLight, Scene3D,
+                                              TriangleMesh)
     from python_ray_tracer_amd.infrastructure.hip import (
         HipRGBColor,
         HipShader,
@@ -258,9 +307,7 @@ def build_scene(spec: dict):
         TextureChecker,
     )
 
-    shapes = []
-    for s in spec["spheres"]:
-        sh = s["shader"]
+    def shader_of(sh):
         tex = sh["texture"]
         if tex["kind"] == "checker":
             texture = TextureChecker()
@@ -273,7 +320,12 @@ def build_scene(spec: dict):
         for key in ("transmission_gain", "specular_ior"):  # optional: glass (glass_spec)
             if key in sh:
                 setattr(shader, key, sh[key])
-        shapes.append(HipSphere(HipVector3D(*s["center"]), s["radius"], shader))
+        return shader
+
+    shapes = [HipSphere(HipVector3D(*s["center"]), s["radius"], shader_of(s["shader"])) for s in spec["spheres"]]
+    for m in spec.get("meshes", ()):  # optional: a mesh scene (mesh_spec)
+        vertices, faces, normals = mesh_arrays(m)
+        shapes.append(TriangleMesh(vertices, faces, shader_of(m["shader"]), normals))
     lights = []
     for li in spec["lights"]:
         if li["kind"] == "point":
