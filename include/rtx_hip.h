@@ -811,6 +811,39 @@ int rtx_trace_mesh(const double* scene, int n_spheres, const double* mesh, int64
                    int n_lights, const double* origins, int64_t origin_stride, const double* dirs, int64_t n,
                    int max_bounces, void* out, int out_kind, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Texture coordinates and image textures on meshes (a TriangleMesh with `uvs` whose texture is an
+ * ImageTexture): rtx_trace_mesh_uv is rtx_trace_mesh, arguments and errors alike, on a table
+ * with two more parts after the nodes, their word offsets in the header words RTX_MH_UVS and RTX_MH_TEXELS
+ * (0 in a table without them, which rtx_trace_mesh renders as before; the host chooses the entry):
+ *   the UV part, RTX_UV_WORDS words per triangle row in the rows' leaf order, row k's at uvs + 6k:
+ *     s0 t0 s1 t1 s2 t2, the texture coordinates at v0, v1, v2 (zeros for a mesh without any);
+ *   the texel part, from RTX_MH_TEXELS to the table's end: one block per distinct image, float64 RGB,
+ *     row-major, row 0 the top of the image.
+ * The material row of an image-textured mesh is RTX_TEX_IMAGE with RTX_M_TR / TG / TB the block's word
+ * offset in the mesh table, the width W and the height H (the sphere record's meaning, the mesh table in
+ * the blob's place; W * H <= RTX_MAX_TEXELS). At a triangle's hit, with u, v of the triangle test above,
+ * the texture's colour is, per channel c, float64 in this order exactly, no contraction:
+ *     w0 = (1 - u) - v
+ *     s  = (w0*s0 + u*s1) + v*s2;  t = (w0*t0 + u*t1) + v*t2
+ *     x  = s*W - 0.5;  y = (1 - t)*H - 0.5                    (t = 0 is the image's bottom row, as in OBJ)
+ *     x0 = floor(x);  fx = x - x0;  y0 = floor(y);  fy = y - y0
+ *     i0 = x0 - W*floor(x0 / W);  i1 = (i0 + 1 == W) ? 0 : i0 + 1       (repeat; one correctly rounded
+ *     j0 = y0 - H*floor(y0 / H);  j1 = (j0 + 1 == H) ? 0 : j0 + 1        division per axis)
+ *     gx = 1 - fx;  gy = 1 - fy
+ *     c  = (c[j0][i0]*gx + c[j0][i1]*fx)*gy + (c[j1][i0]*gx + c[j1][i1]*fx)*fy
+ * It replaces the constant (tr, tg, tb) of that hit; everything after it is rtx_trace_mesh's text. The
+ * host refuses coordinates with |s| or |t| above RTX_MESH_UV_MAX, so x0, y0 and the wrapped indices are
+ * exact integers below 2^31. A sphere with an ImageTexture keeps reading the scene blob (image_texel).
+ * No table makes the kernel read outside it: UV or texel offsets that do not fit mesh_words, or a
+ * material whose block does not lie in the texel part, mean "no image" and the colour is black (the
+ * row's TR / TG / TB words are not a colour); a wrapped index outside its axis (coordinates beyond the
+ * host's limit) reads index 0. */
+enum { RTX_MH_UVS = 8, RTX_MH_TEXELS = 9, RTX_UV_WORDS = 6, RTX_MESH_UV_MAX = 1024 };
+int rtx_trace_mesh_uv(const double* scene, int n_spheres, const double* mesh, int64_t mesh_words,
+                      const double* lights, int n_lights, const double* origins, int64_t origin_stride,
+                      const double* dirs, int64_t n, int max_bounces, void* out, int out_kind, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts
  * gathered row tiles, part p at tiles + p * part_stride_bytes, each as rtx_render_camera wrote it

@@ -23,6 +23,8 @@
 //                        every point light of a table (rtx_trace_lights); allocates its workspace
 //   rt::trace_mesh    <- no counterpart (the reference's only Shape is the sphere): raytrace_scene on explicit rays
 //                        through the spheres and the triangles of a mesh table (rtx_trace_mesh)
+//   rt::trace_mesh_uv <- no counterpart: rt::trace_mesh on a table with texture coordinates and texel blocks
+//                        (rtx_trace_mesh_uv): image textures on meshes
 //   rt::env_sample, rt::trace_lights_env, rt::trace_glass_env
 //                     <- no counterpart (raytrace_scene adds nothing on a miss, base.py:100-121): the environment
 //                        map's lookup alone, and the two kernels above with it for every ray that meets no shape
@@ -856,7 +858,7 @@ int64_t check_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor&
 
 // The mesh table's header against its length: the host-side form of the kernel's own test, which reads a
 // table that fails it as one without triangles (one synchronous copy of the header)
-void check_mesh_header(const at::Tensor& mesh) {
+void check_mesh_header(const at::Tensor& mesh, bool uv = false) {
   const at::Tensor head = mesh.narrow(0, 0, RTX_MESH_HDR_WORDS).to(at::kCPU).contiguous();
   const double* h = head.data_ptr<double>();
   const double w = (double)mesh.numel(), T = h[RTX_MH_NTRI], M = h[RTX_MH_NMESH], N = h[RTX_MH_NNODES];
@@ -866,11 +868,18 @@ void check_mesh_header(const at::Tensor& mesh) {
                   ta >= RTX_MESH_HDR_WORDS && ta + T * RTX_TRI_WORDS <= w && ma >= RTX_MESH_HDR_WORDS &&
                   ma + M * RTX_MAT_WORDS <= w && na >= RTX_MESH_HDR_WORDS && na + N * RTX_NODE_WORDS <= w,
               "mesh table: the header's counts and offsets do not fit its ", mesh.numel(), " words");
+  if (uv) {  // rt::trace_mesh_uv: the UV part and the texel part
+    const double ua = h[RTX_MH_UVS], xa = h[RTX_MH_TEXELS];
+    TORCH_CHECK(ua >= RTX_MESH_HDR_WORDS && ua + T * RTX_UV_WORDS <= w && xa >= RTX_MESH_HDR_WORDS && xa <= w,
+                "mesh table: the offsets of the UV part and the texel blocks do not fit its ", mesh.numel(),
+                " words (a table of meshes.mesh_table with an ImageTexture on a mesh)");
+  }
 }
 
-at::Tensor trace_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
-                      const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
-                      bool check) {
+// rt::trace_mesh (uv false) and rt::trace_mesh_uv
+at::Tensor trace_mesh_call(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                           const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                           bool check, bool uv) {
   check_gpu(scene, "scene", at::kDouble);
   const at::OptionalDeviceGuard guard(at::device_of(scene));
   const struct { const at::Tensor& t; const char* name; } in[] = {
@@ -883,22 +892,35 @@ at::Tensor trace_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tens
   at::Tensor out = new_output(scene, n, -1, 0, out_kind);
   if (check) {
     check_headers(scene, n_spheres);
-    check_mesh_header(mesh);
+    check_mesh_header(mesh, uv);
   }
   if (n == 0) return out;  // (an empty tensor's pointer may be null)
   // the op's own workspace: the zeroed header and the workers' stacks of pending rays
   at::Tensor ws = at::zeros({(int64_t)rtx_mesh_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
-  check_rc(rtx_trace_mesh(scene.data_ptr<double>(), (int)n_spheres, mesh.data_ptr<double>(), mesh.numel(),
-                          lights.data_ptr<double>(), (int)lights.size(0), origins.data_ptr<double>(),
-                          origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n, (int)max_bounces, out.data_ptr(),
-                          (int)out_kind, ws.data_ptr(), (size_t)ws.numel(), stream_of(scene)),
-           "rtx_trace_mesh");
+  check_rc((uv ? rtx_trace_mesh_uv : rtx_trace_mesh)(
+               scene.data_ptr<double>(), (int)n_spheres, mesh.data_ptr<double>(), mesh.numel(),
+               lights.data_ptr<double>(), (int)lights.size(0), origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n,
+               dirs.data_ptr<double>(), n, (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(),
+               (size_t)ws.numel(), stream_of(scene)),
+           uv ? "rtx_trace_mesh_uv" : "rtx_trace_mesh");
   if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
     const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
     TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
                 2 * max_bounces + 2, " pending rays; HipRenderer raises RecursionError)");
   }
   return out;
+}
+
+at::Tensor trace_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                      const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                      bool check) {
+  return trace_mesh_call(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check, false);
+}
+
+at::Tensor trace_mesh_uv(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                         const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                         bool check) {
+  return trace_mesh_call(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check, true);
 }
 
 // ---- the environment map (rtx_env_sample, rtx_trace_lights_env, rtx_trace_glass_env) ----------------
@@ -1294,6 +1316,8 @@ TORCH_LIBRARY(rt, m) {
         "int out_kind, bool check=True) -> Tensor");
   m.def("trace_mesh(Tensor scene, int n_spheres, Tensor mesh, Tensor lights, Tensor origins, Tensor dirs, "
         "int max_bounces, int out_kind, bool check=True) -> Tensor");
+  m.def("trace_mesh_uv(Tensor scene, int n_spheres, Tensor mesh, Tensor lights, Tensor origins, Tensor dirs, "
+        "int max_bounces, int out_kind, bool check=True) -> Tensor");
   m.def("env_sample(Tensor texels, float[] gain, float turn, Tensor dirs) -> Tensor");
   m.def("trace_lights_env(Tensor scene, int n_spheres, Tensor lights, Tensor origins, Tensor dirs, int max_bounces, "
         "int out_kind, Tensor texels, float[] gain, float turn, bool check=True) -> Tensor");
@@ -1335,6 +1359,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("trace_glass", &trace_glass);
   m.impl("trace_lights", &trace_lights);
   m.impl("trace_mesh", &trace_mesh);
+  m.impl("trace_mesh_uv", &trace_mesh_uv);
   m.impl("env_sample", &env_sample);
   m.impl("trace_lights_env", &trace_lights_env);
   m.impl("trace_glass_env", &trace_glass_env);
@@ -1362,6 +1387,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("trace_glass", &trace_glass);
   m.impl("trace_lights", &trace_lights);
   m.impl("trace_mesh", &trace_mesh);
+  m.impl("trace_mesh_uv", &trace_mesh_uv);
   m.impl("env_sample", &env_sample);
   m.impl("trace_lights_env", &trace_lights_env);
   m.impl("trace_glass_env", &trace_glass_env);
@@ -1387,6 +1413,7 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("trace_glass", &trace_glass_meta);
   m.impl("trace_lights", &trace_lights_meta);
   m.impl("trace_mesh", &trace_mesh_meta);
+  m.impl("trace_mesh_uv", &trace_mesh_meta);
   m.impl("env_sample", &env_sample_meta);
   m.impl("trace_lights_env", &trace_lights_env_meta);
   m.impl("trace_glass_env", &trace_glass_env_meta);

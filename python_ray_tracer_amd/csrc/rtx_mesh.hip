@@ -1,5 +1,5 @@
-// rtx_mesh.hip — triangle meshes (rtx_trace_mesh): explicit rays through the spheres of a scene and the
-// triangles of a mesh table, lit by a table of point lights as rtx_trace_lights lights its spheres (the
+// rtx_mesh.hip — triangle meshes (rtx_trace_mesh, rtx_trace_mesh_uv): explicit rays through the spheres of
+// a scene and the triangles of a mesh table, lit by a table of point lights as rtx_trace_lights lights its spheres (the
 // reference's only Shape is the sphere, domain.py:43-50). The triangle test, the group rule, the normals
 // and the shadow rule are written out in include/rtx_hip.h; DESIGN.md §17 has the rest. A translation
 // unit of its own over the shared device text (rtx_device.h), like rtx_lights.hip: the other kernels
@@ -104,6 +104,60 @@ __device__ __forceinline__ MeshView mesh_view(const double* mesh, int64_t words)
   return m;
 }
 
+// The two parts that rtx_trace_mesh_uv's table has after the nodes, checked against the table's length: the
+// word offsets of the UV part (RTX_UV_WORDS per row of m) and of the first texel block; both 0 unless both fit
+struct MeshUvParts {
+  int uv_at, tex_at;
+};
+
+__device__ __forceinline__ MeshUvParts mesh_uv_parts(const double* mesh, int64_t words, const MeshView& m) {
+  const cdouble* h = (const cdouble*)mesh;
+  const double ua = h[RTX_MH_UVS], xa = h[RTX_MH_TEXELS], w = (double)words;
+  const bool ok = m.ntri > 0 && ua >= (double)RTX_MESH_HDR_WORDS && ua == __builtin_floor(ua) &&
+                  ua + (double)m.ntri * RTX_UV_WORDS <= w && xa >= (double)RTX_MESH_HDR_WORDS &&
+                  xa == __builtin_floor(xa) && xa <= w;
+  return ok ? MeshUvParts{(int)ua, (int)xa} : MeshUvParts{0, 0};
+}
+
+// A wrapped texel index as an int: 0 for a value outside 0..n - 1 (only a table whose coordinates exceed
+// RTX_MESH_UV_MAX can make one), so that no table makes the lookup read outside its block
+__device__ __forceinline__ int texel_index(double i, double n) { return i >= 0.0 && i < n ? (int)i : 0; }
+
+// The image colour of include/rtx_hip.h at (u, v) of row `trow`: the mesh's material row `mh` names the
+// texel block (word offset in the table, width, height). Black where the table has no UV part or the block
+// does not lie inside the table's texel part. Per-lane loads: the row's six coordinates and four texels.
+__device__ __forceinline__ void mesh_uv_colour(const double* mesh, int64_t words, const MeshUvParts& parts,
+                                               const double* mh, int trow, double u, double v, double& tr,
+                                               double& tg, double& tb) {
+  tr = tg = tb = 0.0;
+  const double off = mh[RTX_M_TR], W = mh[RTX_M_TG], H = mh[RTX_M_TB];
+  const bool ok = parts.uv_at != 0 && off >= (double)parts.tex_at && off == __builtin_floor(off) && W >= 1.0 &&
+                  H >= 1.0 && W == __builtin_floor(W) && H == __builtin_floor(H) &&
+                  W * H <= (double)RTX_MAX_TEXELS && off + 3.0 * (W * H) <= (double)words;
+  if (!ok) return;
+  const double* c = mesh + (parts.uv_at + (int64_t)trow * RTX_UV_WORDS);
+  const double w0 = (1.0 - u) - v;
+  const double s = (w0 * c[0] + u * c[2]) + v * c[4];
+  const double t = (w0 * c[1] + u * c[3]) + v * c[5];
+  const double x = s * W - 0.5, y = (1.0 - t) * H - 0.5;
+  const double x0 = __builtin_floor(x), y0 = __builtin_floor(y);
+  const double fx = x - x0, fy = y - y0;
+  const double i0 = x0 - W * __builtin_floor(x0 / W), j0 = y0 - H * __builtin_floor(y0 / H);
+  const double i1 = i0 + 1.0 == W ? 0.0 : i0 + 1.0, j1 = j0 + 1.0 == H ? 0.0 : j0 + 1.0;
+  const int wi = (int)W;
+  const int a0 = texel_index(i0, W), a1 = texel_index(i1, W);
+  const int b0 = texel_index(j0, H) * wi, b1 = texel_index(j1, H) * wi;
+  const double* tx = mesh + (int64_t)off;
+  const double* c00 = tx + 3 * (b0 + a0);
+  const double* c01 = tx + 3 * (b0 + a1);
+  const double* c10 = tx + 3 * (b1 + a0);
+  const double* c11 = tx + 3 * (b1 + a1);
+  const double gx = 1.0 - fx, gy = 1.0 - fy;
+  tr = (c00[0] * gx + c01[0] * fx) * gy + (c10[0] * gx + c11[0] * fx) * fy;
+  tg = (c00[1] * gx + c01[1] * fx) * gy + (c10[1] * gx + c11[1] * fx) * fy;
+  tb = (c00[2] * gx + c01[2] * fx) * gy + (c10[2] * gx + c11[2] * fx) * fy;
+}
+
 // The triangle test of include/rtx_hip.h on a row (v0, e1, e2): whether the ray hits, and t, u, v
 template <typename P>
 __device__ __forceinline__ bool tri_test(const P* r, double ox, double oy, double oz, double dx, double dy, double dz,
@@ -194,238 +248,19 @@ __device__ __forceinline__ bool lit_tri(const MeshView& m, double qx, double qy,
 // its nearest distance, in scene order, then the triangle group's if it is as near; the lanes shade one
 // hit per round. A lane on a triangle takes its point's terms from the triangle's row, its material from
 // the mesh's row and a shadow test with t_self = FARAWAY; everything after that is one text for both.
+// The kernel's body is rtx_mesh_walk.inc, included below into k_trace_mesh (UV false: the kernel as it was)
+// and into k_trace_mesh_uv (UV true: a lane on a triangle whose mesh has an image takes its texture colour
+// from the table's UV part and texel blocks, mesh_uv_colour).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kMeshWaves, kMeshWaves)))
 void k_trace_mesh(MeshParams p) {
-  const int64_t w = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (w >= p.n_workers) return;
-  const cdouble* sc = (const cdouble*)p.scene;
-  const cdouble* lt = (const cdouble*)p.lights;
-  // a blob that is not a packed scene of p.nsph spheres: no spheres
-  const int nsph = (sc[RTX_H_MAGIC] == RTX_MAGIC && sc[RTX_H_NSPH] == (double)p.nsph) ? p.nsph : 0;
-  const MeshView m = mesh_view(p.mesh, p.mesh_words);
-  const double* tab = p.scene + RTX_HDR_WORDS;
-  const double* mtab = tab + nsph * RTX_GEOM_WORDS;
-  const int B = p.max_bounces;
-  const int nl = p.n_lights;
-  const int cap = mesh_stack_entries(B);
-  const bool tree = sc[RTX_H_NNODES] != 0.0 && nsph >= kGeneralTreeMin;
-  const double nan = __builtin_nan("");  // the reference expressions in every sphere test (SphTest)
-  const MeshRayStack S{p.stack, p.n_workers, w};
-  Params po{};  // what write_out reads
-  po.out = p.out;
-  po.out_kind = p.out_kind;
-  po.n = p.n;
-  for (int64_t i = w; i < p.n; i += p.n_workers) {
-    {
-      const int64_t s = p.org_stride;
-      const int64_t j = s ? i : 0;
-      S.push(0, p.org[j], p.org[s + j + (s ? 0 : 1)], p.org[2 * s + j + (s ? 0 : 2)], p.dir[i], p.dir[p.n + i],
-             p.dir[2 * p.n + i], 1.0, 1.0, 1.0, 0);
-    }
-    int sp = 1;  // pending rays
-    double ar = 0.0, ag = 0.0, ab = 0.0;
-    // the ray whose hits are being shaded: `left` spheres to go, the next one at or after `next`, then
-    // the triangle of row `trow` if `tri`
-    double ox = 0.0, oy = 0.0, oz = 0.0, dx = 0.0, dy = 0.0, dz = 0.0, oo = 0.0, tmin = FARAWAY;
-    double wr = 0.0, wg = 0.0, wb = 0.0;
-    int level = 0, left = 0, next = 0, trow = 0;
-    bool tri = false;
-    for (;;) {
-      int h = nsph;  // the sphere shaded this round; nsph: the triangle
-      if (left == 0 && !tri) {
-        if (sp == 0) break;
-        --sp;
-        ox = S.at(sp, 0); oy = S.at(sp, 1); oz = S.at(sp, 2);
-        dx = S.at(sp, 3); dy = S.at(sp, 4); dz = S.at(sp, 5);
-        wr = S.at(sp, 6); wg = S.at(sp, 7); wb = S.at(sp, 8);
-        level = (int)S.at(sp, 9);
-        oo = dot3(ox, oy, oz, ox, oy, oz);
-        // the spheres' nearest distance (base.py:97-98), how many share it and the first in scene order
-        tmin = FARAWAY;
-        int nh = 0, first = nsph;
-        nearest_count(sc, nsph, tree, ox, oy, oz, oo, dx, dy, dz, tmin, nh, first);
-        // the triangle group at or before it
-        double tt = FARAWAY;
-        int num = 0x7fffffff;
-        nearest_tri(m, ox, oy, oz, oo, dx, dy, dz, tmin, tt, num, trow);
-        tri = tt != FARAWAY && tt <= tmin;
-        if (tt < tmin) {  // (the spheres are farther: none shades)
-          tmin = tt;
-          nh = 0;
-        }
-        left = tmin != FARAWAY ? nh : 0;  // (nearest != FARAWAY) & (t == nearest), base.py:102-103
-        if (left == 0 && !tri) continue;
-        next = first;
-      }
-      if (left > 0) {  // the next sphere in scene order at the nearest distance
-        for (int s = next; s < nsph; ++s) {
-          if (isect(tab + s * RTX_GEOM_WORDS, ox, oy, oz, oo, dx, dy, dz) == tmin) {
-            h = s;
-            break;
-          }
-        }
-        if (h == nsph) {  // (cannot happen: `left` counted it)
-          left = 0;
-          continue;
-        }
-        next = h + 1;
-        --left;
-      } else {
-        tri = false;
-      }
-      const bool on_tri = h == nsph;
+  constexpr bool UV = false;
+#include "rtx_mesh_walk.inc"
+}
 
-      // NumpyShader.create (shader.py:63-112) of the hit, the light's terms once per table row
-      const double px = ox + dx * tmin, py = oy + dy * tmin, pz = oz + dz * tmin;  // :73
-      const double* gh = tab;  // (read by the lanes on a sphere only)
-      const double* mh;
-      double nx, ny, nz, qx, qy, qz;
-      if (on_tri) {
-        const double* r = p.mesh + (m.tris_at + (int64_t)trow * RTX_TRI_WORDS);
-        int mi = (int)r[RTX_T_MESH];
-        mi = mi < 0 ? 0 : (mi < m.nmesh ? mi : m.nmesh - 1);
-        mh = m.mats + mi * RTX_MAT_WORDS;
-        double gx = r[RTX_T_NG], gy = r[RTX_T_NG + 1], gz = r[RTX_T_NG + 2];
-        if (dot3(gx, gy, gz, dx, dy, dz) > 0.0) {  // the face normal opposes the ray
-          gx = -gx;
-          gy = -gy;
-          gz = -gz;
-        }
-        nx = gx;
-        ny = gy;
-        nz = gz;
-        if (r[RTX_T_SMOOTH] != 0.0) {
-          double t, u, v;
-          tri_test(r, ox, oy, oz, dx, dy, dz, t, u, v);
-          const double w0 = (1.0 - u) - v;
-          nx = (w0 * r[RTX_T_N0] + u * r[RTX_T_N1]) + v * r[RTX_T_N2];
-          ny = (w0 * r[RTX_T_N0 + 1] + u * r[RTX_T_N1 + 1]) + v * r[RTX_T_N2 + 1];
-          nz = (w0 * r[RTX_T_N0 + 2] + u * r[RTX_T_N1 + 2]) + v * r[RTX_T_N2 + 2];
-          norm3(nx, ny, nz, nan);
-          if (dot3(nx, ny, nz, gx, gy, gz) < 0.0) {
-            nx = -nx;
-            ny = -ny;
-            nz = -nz;
-          }
-        }
-        qx = px + gx * 0.0001;  // :77 with the face normal
-        qy = py + gy * 0.0001;
-        qz = pz + gz * 0.0001;
-      } else {
-        gh = tab + h * RTX_GEOM_WORDS;
-        mh = mtab + h * RTX_MAT_WORDS;
-        const double inv_r = gh[RTX_G_INVR];
-        nx = (px - gh[RTX_G_CX]) * inv_r;  // :74 (not renormalised)
-        ny = (py - gh[RTX_G_CY]) * inv_r;
-        nz = (pz - gh[RTX_G_CZ]) * inv_r;
-        qx = px + nx * 0.0001;  // :77
-        qy = py + ny * 0.0001;
-        qz = pz + nz * 0.0001;
-      }
-      const double qq = dot3(qx, qy, qz, qx, qy, qz);
-      // the sphere whose own test the shadow searches skip: the wave's, when its lanes agree (a lane on a
-      // triangle agrees with none)
-      const int h0 = __builtin_amdgcn_readfirstlane(h);
-      const int hs = __ballot(h != h0) == 0 ? h0 : nsph;
-      const double g = mh[RTX_M_G];
-      const double dg = mh[RTX_M_DG];
-      const double igain = mh[RTX_M_IG];
-      double vx = sc[RTX_H_CAM + 0] - px, vy = sc[RTX_H_CAM + 1] - py, vz = sc[RTX_H_CAM + 2] - pz;
-      {  // :76 (towards the camera on every level)
-        const double rv = inv_mag_shade(dot3(vx, vy, vz, vx, vy, vz));
-        vx = vx * rv;
-        vy = vy * rv;
-        vz = vz * rv;
-      }
-      // the texture's colour at the hit (TextureChecker :29-32, ImageTexture shape.py:66-79, Texture :17-19)
-      double tr, tg, tb;
-      const double tex = mh[RTX_M_TEX];
-      if (tex == RTX_TEX_CHECKER) {
-        tr = tg = tb = (trunc_parity(px * 2.0) == trunc_parity(pz * 2.0)) ? 1.0 : 0.0;
-      } else if (tex == RTX_TEX_IMAGE && !on_tri) {
-        const double* t = p.scene + ((int64_t)mh[RTX_M_TR] + 3 * (int64_t)image_texel(mh, gh, px, py, pz));
-        tr = t[0];
-        tg = t[1];
-        tb = t[2];
-      } else {
-        tr = mh[RTX_M_TR];
-        tg = mh[RTX_M_TG];
-        tb = mh[RTX_M_TB];
-      }
-      double dr = 0.0, dgr = 0.0, db = 0.0;  // diffuse, summed over the lights
-      double xr = 0.0, xg = 0.0, xb = 0.0;   // glossy with a black reflection
-      double er = 0.0, eg = 0.0, eb = 0.0;   // sum_i lit_i e_i: what the reflected colour is weighted by
-      for (int li = 0; li < nl; ++li) {
-        const cdouble* row = lt + __builtin_amdgcn_readfirstlane(li) * kLightWords;
-        const double e0 = row[3], e1 = row[4], e2 = row[5];
-        double lx = row[0] - px, ly = row[1] - py, lz = row[2] - pz;
-        norm3(lx, ly, lz, nan);  // :75
-        // _calculate_shadow (:126-128) in its any-hit form: lit unless some shape is strictly nearer than
-        // the hit sphere itself along L from the nudged point; a triangle's own distance is FARAWAY
-        double tself = FARAWAY;
-        if (!on_tri) tself = isect_t(gh, qx, qy, qz, qq, lx, ly, lz, nan);
-        bool lit = nothing_nearer(sc, nsph, qx, qy, qz, qq, lx, ly, lz, tself, hs);
-        if (__ballot(lit) != 0) lit = lit_tri(m, qx, qy, qz, qq, lx, ly, lz, tself, lit);
-        if (__ballot(lit) == 0) continue;  // no lane of the wave is lit by this light: every term is x * 0
-        const double litf = lit ? 1.0 : 0.0;
-        const double dli = max0(dot3(nx, ny, nz, lx, ly, lz));  // :138
-        dr = dr + (((tr * dli) * litf) * dg) * e0;
-        dgr = dgr + (((tg * dli) * litf) * dg) * e1;
-        db = db + (((tb * dli) * litf) * dg) * e2;
-        if (__ballot(lit && g != 0.0) != 0) {
-          const double spec = (lit && g != 0.0) ? specular(mh, g, nx, ny, nz, lx, ly, lz, vx, vy, vz, nan) : 0.0;
-          const double sg = (spec * g) * litf;  // :106 with R = 0
-          xr = xr + sg * e0;
-          xg = xg + sg * e1;
-          xb = xb + sg * e2;
-        }
-        er = er + litf * e0;
-        eg = eg + litf * e1;
-        eb = eb + litf * e2;
-      }
-      // dome (:239-242), light_direction (0, 1, 0): N.(0, 1, 0) is ny for finite N
-      const int ndome = (int)sc[RTX_H_NDOME];
-      double di = 0.0;
-      for (int j = 0; j < ndome; ++j) di = di + sc[RTX_H_DOMEI + j] * max0(ny);
-      // thin-film iridescence (:186-232); zero when iridescence_gain == 0
-      double ir = 0.0, ig = 0.0, ib = 0.0;
-      if (igain != 0.0) {
-        const double va = clip01(dot3(nx, ny, nz, vx, vy, vz));  // :201
-        const double af = fabs(va - 0.5) * 2.0;  // :204
-        const double phase = ((af * RTX_PI) * mh[RTX_M_TFT]) * 10.0;  // :208
-        const double ip = sin_ref(sc, phase, nan);  // :211
-        const double hsh = mh[RTX_M_HS], omhs = mh[RTX_M_1MHS];
-        const double r = ip * hsh + omhs * (1.0 - ip);  // :221
-        const double gg = ip * omhs + hsh * (1.0 - ip);  // :222
-        const double b = 0.5 + 0.5 * ip;  // :223
-        const double tw = mh[RTX_M_TFW];
-        ir = (r * tw) * igain;  // :229-232
-        ig = (gg * tw) * igain;
-        ib = (b * tw) * igain;
-      }
-      const double cr = (((0.004 + dr) + sc[RTX_H_DOMEC + 0] * di) + xr) + ir;
-      const double cg = (((0.004 + dgr) + sc[RTX_H_DOMEC + 1] * di) + xg) + ig;
-      const double cb = (((0.004 + db) + sc[RTX_H_DOMEC + 2] * di) + xb) + ib;
-      ar = ar + wr * cr;
-      ag = ag + wg * cg;
-      ab = ab + wb * cb;
-      if (level >= B) continue;  // the next level is black
-      // the reflected ray, (R * 0.5) * g per light that reaches the hit (shader.py:106); not traced where
-      // it is multiplied by zero
-      if (g != 0.0 && (er != 0.0 || eg != 0.0 || eb != 0.0)) {
-        if (sp < cap) {
-          double rx = dx, ry = dy, rz = dz;
-          reflect_dir(rx, ry, rz, nx, ny, nz, nan);
-          S.push(sp, qx, qy, qz, rx, ry, rz, ((wr * 0.5) * g) * er, ((wg * 0.5) * g) * eg, ((wb * 0.5) * g) * eb,
-                 level + 1);
-          ++sp;
-        } else {
-          atomicOr(p.status, (uint32_t)RTX_ST_STACK_OVERFLOW);
-        }
-      }
-    }
-    write_out(po, i, ar, ag, ab);
-  }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kMeshWaves, kMeshWaves)))
+void k_trace_mesh_uv(MeshParams p) {
+  constexpr bool UV = true;
+#include "rtx_mesh_walk.inc"
 }
 
 }  // namespace
@@ -436,10 +271,13 @@ extern "C" size_t rtx_mesh_workspace_bytes(int64_t n_rays, int max_bounces) {
          (size_t)mesh_workers(n_rays, max_bounces) * mesh_stack_entries(max_bounces) * kMeshRayWords * 8;
 }
 
-extern "C" int rtx_trace_mesh(const double* scene, int n_spheres, const double* mesh, int64_t mesh_words,
-                              const double* lights, int n_lights, const double* origins, int64_t origin_stride,
-                              const double* dirs, int64_t n, int max_bounces, void* out, int out_kind, void* workspace,
-                              size_t workspace_bytes, void* stream) {
+namespace {
+
+// rtx_trace_mesh (uv false) and rtx_trace_mesh_uv behind one set of checks
+int trace_mesh_call(const double* scene, int n_spheres, const double* mesh, int64_t mesh_words, const double* lights,
+                    int n_lights, const double* origins, int64_t origin_stride, const double* dirs, int64_t n,
+                    int max_bounces, void* out, int out_kind, void* workspace, size_t workspace_bytes, void* stream,
+                    bool uv) {
   if (!scene) return rtx_fail(RTX_E_ARG, "null scene pointer");
   if (!mesh) return rtx_fail(RTX_E_ARG, "null mesh table pointer");
   if (!lights) return rtx_fail(RTX_E_ARG, "null lights table pointer");
@@ -481,6 +319,29 @@ extern "C" int rtx_trace_mesh(const double* scene, int n_spheres, const double* 
   p.status = (uint32_t*)workspace + RTX_WS_STATUS;
   p.stack = (double*)((uint8_t*)workspace + RTX_WS_HDR_BYTES);
   p.n_workers = mesh_workers(n, max_bounces);
-  hipLaunchKernelGGL(k_trace_mesh, dim3((unsigned)(p.n_workers / 64)), dim3(64), 0, (hipStream_t)stream, p);
+  const dim3 grid((unsigned)(p.n_workers / 64));
+  if (uv) {
+    hipLaunchKernelGGL(k_trace_mesh_uv, grid, dim3(64), 0, (hipStream_t)stream, p);
+    return rtx_launched("k_trace_mesh_uv");
+  }
+  hipLaunchKernelGGL(k_trace_mesh, grid, dim3(64), 0, (hipStream_t)stream, p);
   return rtx_launched("k_trace_mesh");
+}
+
+}  // namespace
+
+extern "C" int rtx_trace_mesh(const double* scene, int n_spheres, const double* mesh, int64_t mesh_words,
+                              const double* lights, int n_lights, const double* origins, int64_t origin_stride,
+                              const double* dirs, int64_t n, int max_bounces, void* out, int out_kind, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  return trace_mesh_call(scene, n_spheres, mesh, mesh_words, lights, n_lights, origins, origin_stride, dirs, n,
+                         max_bounces, out, out_kind, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int rtx_trace_mesh_uv(const double* scene, int n_spheres, const double* mesh, int64_t mesh_words,
+                                 const double* lights, int n_lights, const double* origins, int64_t origin_stride,
+                                 const double* dirs, int64_t n, int max_bounces, void* out, int out_kind,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  return trace_mesh_call(scene, n_spheres, mesh, mesh_words, lights, n_lights, origins, origin_stride, dirs, n,
+                         max_bounces, out, out_kind, workspace, workspace_bytes, stream, true);
 }

@@ -149,17 +149,26 @@ class TriangleMesh(Shape):
 
     ``vertices``: float [V, 3]. ``faces``: int [F, 3], indices into ``vertices``. ``normals``: float
     [V, 3] for smooth shading (the shading normal is interpolated over a face), None for flat.
-    ``shader``: the material of every face, a ``HipShader`` (a plain or a checker texture; no image
-    texture, no transmission). The arrays are kept as float64 / int64 copies; they are validated where a
-    table is built from them (``meshes.mesh_table``)."""
+    ``uvs``: texture coordinates per corner, float [F, 3, 2]: ``(s, t)`` at ``v0, v1, v2`` of each face
+    (OBJ's ``vt``: t = 0 is the image's bottom row; a closed surface can have a seam without split
+    vertices), or float [V, 2] per vertex, expanded to ``uvs[faces]``; None for a mesh without any.
+    ``shader``: the material of every face, a ``HipShader`` (a plain or a checker texture, or an
+    ``ImageTexture`` on a mesh with ``uvs``, looked up bilinearly with repeat: include/rtx_hip.h,
+    DESIGN.md §18; no transmission). The arrays are kept as float64 / int64 copies; they are validated
+    where a table is built from them (``meshes.mesh_table``)."""
 
-    def __init__(self, vertices, faces, shader, normals=None) -> None:
+    def __init__(self, vertices, faces, shader, normals=None, uvs=None) -> None:
         import numpy as np
 
         self.vertices = np.array(vertices, dtype=np.float64)
         self.faces = np.array(faces, dtype=np.int64)
         self.shader = shader
         self.normals = None if normals is None else np.array(normals, dtype=np.float64)
+        self.uvs = None if uvs is None else np.array(uvs, dtype=np.float64)
+        if (self.uvs is not None and self.uvs.ndim == 2 and self.uvs.shape == (len(self.vertices), 2)
+                and self.faces.ndim == 2 and self.faces.size and 0 <= self.faces.min()
+                and self.faces.max() < len(self.vertices)):
+            self.uvs = self.uvs[self.faces]  # per vertex -> per corner
 
     def intersect(self, ray_origin, normalized_ray_direction):
         """The distance to the nearest triangle of this mesh (the two-sided Möller–Trumbore test of
@@ -176,11 +185,11 @@ class TriangleMesh(Shape):
         import numpy as np
 
         v = self.vertices * float(scale) + np.asarray(translation, dtype=np.float64).reshape(1, 3)
-        return TriangleMesh(v, self.faces, self.shader, self.normals)
+        return TriangleMesh(v, self.faces, self.shader, self.normals, self.uvs)
 
     def __repr__(self) -> str:
         return (f"TriangleMesh(<{len(self.vertices)} vertices, {len(self.faces)} faces, "
-                f"{'smooth' if self.normals is not None else 'flat'}>)")
+                f"{'smooth' if self.normals is not None else 'flat'}{', uvs' if self.uvs is not None else ''}>)")
 
 
 @dataclass

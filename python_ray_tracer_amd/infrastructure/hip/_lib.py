@@ -129,6 +129,7 @@ EXPORTS = (
     "rtx_trace_glass_env",
     "rtx_mesh_workspace_bytes",
     "rtx_trace_mesh",
+    "rtx_trace_mesh_uv",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -231,6 +232,8 @@ _SIGS = {
     "rtx_mesh_workspace_bytes": (_size, [_i64, _i32]),
     "rtx_trace_mesh": (_i32, [_c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
                               _c_void_p, _i32, _c_void_p, _size, _c_void_p]),
+    "rtx_trace_mesh_uv": (_i32, [_c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64,
+                                 _i32, _c_void_p, _i32, _c_void_p, _size, _c_void_p]),
 }
 
 _lib = None

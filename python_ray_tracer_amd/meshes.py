@@ -22,6 +22,12 @@ MAGIC = 1296388936.0  # RTX_MESH_MAGIC
 HDR_WORDS = 16  # RTX_MESH_HDR_WORDS
 # header words (RTX_MH_*)
 MH_MAGIC, MH_NTRI, MH_NMESH, MH_NNODES, MH_TRIS, MH_MATS, MH_NODES, MH_WORDS = range(8)
+# ... of a table with image textures (rtx_trace_mesh_uv): the word offsets of the UV part and
+# of the texel blocks, 0 in a table without them
+MH_UVS, MH_TEXELS = 8, 9
+UV_WORDS = 6  # RTX_UV_WORDS: s0 t0 s1 t1 s2 t2 per triangle row
+UV_MAX = 1024.0  # RTX_MESH_UV_MAX: the largest |s|, |t| (the lookup's indices stay exact ints)
+MAX_TEXELS = 1 << 20  # RTX_MAX_TEXELS
 TRI_WORDS = 24  # RTX_TRI_WORDS
 # triangle row words (RTX_T_*): v0, e1 = v1 - v0, e2 = v2 - v0, the unit face normal, the mesh, 1 for
 # vertex normals, the three vertex normals, the triangle's number in the group
@@ -109,15 +115,18 @@ def vertex_normals(vertices, faces) -> np.ndarray:
 
 
 def load_obj(path, shader, smooth: bool = False) -> TriangleMesh:
-    """The mesh of a Wavefront OBJ file: ``v`` and ``vn`` records, ``f`` records with ``v``, ``v/vt``,
+    """The mesh of a Wavefront OBJ file: ``v``, ``vn`` and ``vt`` records, ``f`` records with ``v``, ``v/vt``,
     ``v//vn`` and ``v/vt/vn`` indices (1-based, or negative: counted back from the latest record),
     polygons fan-triangulated from their first corner; comments and every other record are ignored.
+    ``uvs`` (per corner, the first two numbers of a ``vt``) are kept if every corner of every face names a
+    ``vt`` that exists, else the mesh has none.
     ``smooth``: with vertex normals, the file's ``vn`` where every corner names one (a vertex that
     several corners give different normals is split), else area-weighted ones (``vertex_normals``).
     ValueError for a record that does not parse and for an index out of range."""
     verts, norms, corners, faces = [], [], {}, []
     out_v, out_n = [], []
     any_vn, all_vn = False, True
+    texs, face_uvs, all_vt = [], [], True
 
     def index(tok: str, count: int, what: str, line_no: int) -> int:
         try:
@@ -142,13 +151,26 @@ def load_obj(path, shader, smooth: bool = False) -> TriangleMesh:
                 if len(xyz) != 3:
                     raise ValueError(f"{path}:{line_no}: a {parts[0]} record needs three numbers")
                 (verts if parts[0] == "v" else norms).append(xyz)
+            elif parts[0] == "vt":  # (never an error: a record that does not parse leaves the mesh without uvs)
+                try:
+                    st = [float(x) for x in parts[1:3]]
+                except ValueError:
+                    st = []
+                texs.append(st if len(st) == 2 else None)
             elif parts[0] == "f":
                 if len(parts) < 4:
                     raise ValueError(f"{path}:{line_no}: a face needs at least three corners")
-                poly = []
+                poly, poly_uv = [], []
                 for tok in parts[1:]:
                     fields = tok.split("/")
                     vi = index(fields[0], len(verts), "vertex", line_no)
+                    st = None
+                    if len(fields) >= 2 and fields[1].lstrip("-").isdigit() and int(fields[1]) != 0:
+                        ti = int(fields[1])
+                        ti = ti - 1 if ti > 0 else len(texs) + ti
+                        st = texs[ti] if 0 <= ti < len(texs) else None
+                    all_vt = all_vt and st is not None
+                    poly_uv.append(st)
                     ni = None
                     if len(fields) >= 3 and fields[2] != "":
                         ni = index(fields[2], len(norms), "normal", line_no)
@@ -162,6 +184,7 @@ def load_obj(path, shader, smooth: bool = False) -> TriangleMesh:
                         out_n.append(norms[ni] if ni is not None else (0.0, 0.0, 0.0))
                     poly.append(corners[key])
                 faces += [(poly[0], poly[i], poly[i + 1]) for i in range(1, len(poly) - 1)]
+                face_uvs += [(poly_uv[0], poly_uv[i], poly_uv[i + 1]) for i in range(1, len(poly) - 1)]
     use_vn = smooth and any_vn and all_vn
     if not use_vn:  # the file's vertices in the file's order: corners that differ in their normal alone are one
         remap = np.zeros(len(out_v), dtype=np.int64)
@@ -176,22 +199,28 @@ def load_obj(path, shader, smooth: bool = False) -> TriangleMesh:
         normals = np.asarray(out_n, dtype=np.float64).reshape(-1, 3)
     elif smooth:
         normals = vertex_normals(v, f)
-    return TriangleMesh(v, f, shader, normals)
+    uvs = np.asarray(face_uvs, dtype=np.float64).reshape(-1, 3, 2) if all_vt and face_uvs else None
+    return TriangleMesh(v, f, shader, normals, uvs)
 
 
-def quad(corners, shader) -> TriangleMesh:
-    """Two triangles (0, 1, 2) and (0, 2, 3) over four corners given in order round the quad."""
+_QUAD_UV = np.array([[(0, 0), (1, 0), (1, 1)], [(0, 0), (1, 1), (0, 1)]], dtype=np.float64)  # faces (0,1,2), (0,2,3)
+
+
+def quad(corners, shader, uv: bool = False) -> TriangleMesh:
+    """Two triangles (0, 1, 2) and (0, 2, 3) over four corners given in order round the quad. ``uv``: the
+    corners get the texture coordinates (0, 0), (1, 0), (1, 1), (0, 1)."""
     c = np.asarray(corners, dtype=np.float64).reshape(4, 3)
-    return TriangleMesh(c, [(0, 1, 2), (0, 2, 3)], shader)
+    return TriangleMesh(c, [(0, 1, 2), (0, 2, 3)], shader, None, _QUAD_UV if uv else None)
 
 
-def box(lo, hi, shader) -> TriangleMesh:
-    """The axis-aligned box from ``lo`` to ``hi``: 8 vertices, 12 triangles, normals outwards."""
+def box(lo, hi, shader, uv: bool = False) -> TriangleMesh:
+    """The axis-aligned box from ``lo`` to ``hi``: 8 vertices, 12 triangles, normals outwards. ``uv``: every
+    face gets the texture coordinates 0..1, as ``quad`` gives them to its corners in the face's order."""
     (x0, y0, z0), (x1, y1, z1) = (tuple(float(x) for x in lo), tuple(float(x) for x in hi))
     v = [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)]
     q = [(0, 3, 2, 1), (4, 5, 6, 7), (0, 1, 5, 4), (2, 3, 7, 6), (1, 2, 6, 5), (0, 4, 7, 3)]
     f = [t for a, b, c, d in q for t in ((a, b, c), (a, c, d))]
-    return TriangleMesh(v, f, shader)
+    return TriangleMesh(v, f, shader, None, np.tile(_QUAD_UV, (6, 1, 1)) if uv else None)
 
 
 def icosphere(level: int, shader, smooth: bool = False) -> TriangleMesh:
@@ -221,10 +250,12 @@ def icosphere(level: int, shader, smooth: bool = False) -> TriangleMesh:
     return TriangleMesh(v, f, shader, v.copy() if smooth else None)
 
 
-def torus(R: float, r: float, nu: int, nv: int, shader, smooth: bool = False) -> TriangleMesh:
+def torus(R: float, r: float, nu: int, nv: int, shader, smooth: bool = False, uv: bool = False) -> TriangleMesh:
     """A torus about the y axis through the origin: ``R`` the radius of the tube's centre circle, ``r``
     the tube's, ``nu`` segments round the axis and ``nv`` round the tube: 2 * nu * nv triangles.
-    ``smooth``: the vertex normals point from the tube's centre circle."""
+    ``smooth``: the vertex normals point from the tube's centre circle. ``uv``: texture coordinates per
+    corner, s = i / nu round the axis and t = j / nv round the tube; the last segment ends at 1, not 0 (the
+    seam needs no split vertex)."""
     if int(nu) != nu or int(nv) != nv or nu < 3 or nv < 3:
         raise ValueError(f"torus: nu and nv must be ints >= 3, got {nu!r} and {nv!r}")
     nu, nv = int(nu), int(nv)
@@ -237,7 +268,13 @@ def torus(R: float, r: float, nu: int, nv: int, shader, smooth: bool = False) ->
     i1, j1 = (i + 1) % nu, (j + 1) % nv
     p00, p10, p11, p01 = (i * nv + j).ravel(), (i1 * nv + j).ravel(), (i1 * nv + j1).ravel(), (i * nv + j1).ravel()
     f = np.concatenate([np.stack([p00, p11, p10], 1), np.stack([p00, p01, p11], 1)])
-    return TriangleMesh(v, f, shader, n if smooth else None)
+    uvs = None
+    if uv:
+        s0, s1, t0, t1 = (i / nu).ravel(), ((i + 1) / nu).ravel(), (j / nv).ravel(), ((j + 1) / nv).ravel()
+        st = lambda a, b: np.stack([a, b], 1)  # noqa: E731
+        uvs = np.concatenate([np.stack([st(s0, t0), st(s1, t1), st(s1, t0)], 1),
+                              np.stack([st(s0, t0), st(s0, t1), st(s1, t1)], 1)])
+    return TriangleMesh(v, f, shader, n if smooth else None, uvs)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -267,8 +304,46 @@ def _mesh_arrays(mesh, i: int):
     return v, f.astype(np.int64), n
 
 
+def _is_image(tex) -> bool:
+    return hasattr(tex, "texels")
+
+
+def has_image(shapes) -> bool:
+    """Whether some mesh of ``shapes`` has an ``ImageTexture``: the scene's table gets a UV part and texel
+    blocks and is traced by rtx_trace_mesh_uv."""
+    return any(isinstance(sh, TriangleMesh) and _is_image(getattr(sh.shader, "diffuse_color", None)) for sh in shapes)
+
+
+def _mesh_uvs(mesh, i: int, F: int):
+    """The texture coordinates [F, 3, 2] of mesh ``i`` (``F`` faces), validated, or None."""
+    uv = getattr(mesh, "uvs", None)
+    if uv is None:
+        return None
+    uv = np.asarray(uv, dtype=np.float64)
+    if uv.shape != (F, 3, 2):
+        raise ValueError(f"mesh {i}: uvs must be [F, 3, 2] per corner ({F} faces) or [V, 2] per vertex, got {uv.shape}")
+    if not np.isfinite(uv).all():
+        raise ValueError(f"mesh {i}: a texture coordinate (uvs) is not finite")
+    if np.abs(uv).max() > UV_MAX:
+        raise ValueError(f"mesh {i}: a texture coordinate (uvs) lies outside -{UV_MAX:g}..{UV_MAX:g} (RTX_MESH_UV_MAX)")
+    return uv
+
+
+def _mesh_image(mesh, i: int):
+    """The texels float64 [H, W, 3] of mesh ``i``'s ImageTexture, validated."""
+    t = np.asarray(mesh.shader.diffuse_color.texels, dtype=np.float64)
+    if t.ndim != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"mesh {i}: the ImageTexture's texels must be [H, W, 3], got {t.shape}")
+    if t.shape[0] * t.shape[1] > MAX_TEXELS:
+        raise ValueError(f"mesh {i}: the ImageTexture has {t.shape[0] * t.shape[1]} texels, more than {MAX_TEXELS} "
+                         "(RTX_MAX_TEXELS)")
+    return t
+
+
 def _mesh_material(mesh, i: int) -> list:
-    """The material row of mesh ``i``'s shader (the spheres' record, scene_pack._material_row)."""
+    """The material row of mesh ``i``'s shader (the spheres' record, scene_pack._material_row). An
+    ImageTexture's row is RTX_TEX_IMAGE with a block offset of 0, the width and the height: ``mesh_table``
+    writes the offset of the image's texel block."""
     from python_ray_tracer_amd.infrastructure.hip import _lib as L
     from python_ray_tracer_amd.infrastructure.hip.scene_pack import _material_row
 
@@ -278,8 +353,12 @@ def _mesh_material(mesh, i: int) -> list:
         raise ValueError(f"mesh {i}: transmission_gain != 0; there is no refraction through a mesh")
     if type(tex).__name__ == "TextureChecker":
         tex_fields = (L.TEX_CHECKER, 1.0, 1.0, 1.0)
-    elif hasattr(tex, "texels"):
-        raise ValueError(f"mesh {i}: an ImageTexture needs texture coordinates, which a mesh does not have")
+    elif _is_image(tex):
+        if getattr(mesh, "uvs", None) is None:
+            raise ValueError(f"mesh {i}: an ImageTexture needs texture coordinates, which this mesh does not have "
+                             "(TriangleMesh(..., uvs=...))")
+        t = _mesh_image(mesh, i)
+        tex_fields = (L.TEX_IMAGE, None, float(t.shape[1]), float(t.shape[0]))
     elif hasattr(tex, "color"):
         tex_fields = (L.TEX_CONST, float(tex.color.x), float(tex.color.y), float(tex.color.z))
     else:
@@ -290,16 +369,19 @@ def _mesh_material(mesh, i: int) -> list:
 
 
 def triangle_rows(shapes):
-    """(rows float64 [T, TRI_WORDS] in group order, material rows [M, MAT_WORDS]) of the meshes of
-    ``shapes``, validated. ValueError as ``mesh_table``."""
-    rows, mats, base = [], [], 0
+    """(rows float64 [T, TRI_WORDS] in group order, material rows [M, MAT_WORDS], the rows' texture
+    coordinates [T, UV_WORDS], zeros for a mesh without any) of the meshes of ``shapes``, validated.
+    ValueError as ``mesh_table``."""
+    rows, mats, uvs, base = [], [], [], 0
     meshes = [sh for sh in shapes if isinstance(sh, TriangleMesh)]
     if not meshes:
         raise ValueError("no TriangleMesh among the shapes")
     for i, mesh in enumerate(meshes):
         v, f, n = _mesh_arrays(mesh, i)
-        mats.append(_mesh_material(mesh, i))
         F = f.shape[0]
+        uv = _mesh_uvs(mesh, i, F)
+        mats.append(_mesh_material(mesh, i))
+        uvs.append(np.zeros((F, UV_WORDS)) if uv is None else uv.reshape(F, UV_WORDS))
         if base + F > MAX_TRIANGLES:
             raise ValueError(f"at most {MAX_TRIANGLES} triangles per scene (RTX_MAX_TRIANGLES), got more")
         v0 = v[f[:, 0]]
@@ -320,7 +402,7 @@ def triangle_rows(shapes):
         r[:, T_NUM] = base + np.arange(F)
         rows.append(r)
         base += F
-    return np.concatenate(rows), np.asarray(mats, dtype=np.float64).reshape(len(mats), -1)
+    return np.concatenate(rows), np.asarray(mats, dtype=np.float64).reshape(len(mats), -1), np.concatenate(uvs)
 
 
 def build_tree(lo, hi, max_leaf):
@@ -360,19 +442,28 @@ def build_tree(lo, hi, max_leaf):
 
 
 def _content_digest(shapes) -> str:
-    """The digest of everything a table is built from: every mesh's arrays and material row."""
+    """The digest of everything a table is built from: every mesh's arrays and material row, its texture
+    coordinates and its image's digest."""
     h = hashlib.blake2b(digest_size=16)
     k = 0
     for sh in shapes:
         if not isinstance(sh, TriangleMesh):
             continue
         h.update(np.asarray(_mesh_material(sh, k), dtype=np.float64).tobytes())
-        for a in (sh.vertices, sh.faces, sh.normals):
+        tex = sh.shader.diffuse_color
+        if _is_image(tex):
+            h.update(b"image" + str(getattr(tex, "digest", None) or _texels_digest(tex.texels)).encode())
+        for a in (sh.vertices, sh.faces, sh.normals, getattr(sh, "uvs", None)):
             a = np.ascontiguousarray(np.zeros(0) if a is None else a)
             h.update(repr((a.dtype.str, a.shape)).encode())
             h.update(a.tobytes())
         k += 1
     return h.hexdigest()
+
+
+def _texels_digest(texels) -> str:
+    t = np.ascontiguousarray(texels, dtype=np.float64)
+    return hashlib.blake2b(t.tobytes() + repr(t.shape).encode(), digest_size=16).hexdigest()
 
 
 def mesh_table(shapes, max_leaf=4) -> np.ndarray:
@@ -382,8 +473,14 @@ def mesh_table(shapes, max_leaf=4) -> np.ndarray:
     first, count, skip, margin). ``max_leaf``: the most triangles of a leaf (None: one leaf). Cached by
     content. ValueError for vertices that are not finite, face indices out of range, a mesh without
     faces, a degenerate face (one whose normal cannot be normalised; none is dropped), normals of the
-    wrong shape, an image texture or a transmissive shader on a mesh, and more than MAX_TRIANGLES
-    triangles."""
+    wrong shape, a transmissive shader on a mesh, and more than MAX_TRIANGLES triangles.
+    If some mesh's texture is an ``ImageTexture`` (``has_image``), the table is rtx_trace_mesh_uv's: after
+    the nodes come a UV part, UV_WORDS words per triangle row in the rows' leaf order (zeros for a mesh
+    without ``uvs``), and one texel block per distinct image (float64 RGB, row-major, row 0 the top), the
+    two offsets in the header words MH_UVS and MH_TEXELS, and such a mesh's material row holds its block's
+    word offset, width and height. Then also ValueError for an ImageTexture on a mesh without ``uvs``, for
+    ``uvs`` of the wrong shape, not finite or beyond UV_MAX, for an image of more than MAX_TEXELS texels
+    and for a table of 2^31 words or more. Otherwise the table is the one of a scene without ``uvs``."""
     return mesh_table_entry(shapes, max_leaf)[0]
 
 
@@ -398,7 +495,8 @@ def mesh_table_entry(shapes, max_leaf=4) -> tuple:
     hit = _TABLES.get(key)
     if hit is not None:
         return hit, key
-    rows, mats = triangle_rows(shapes)
+    image = has_image(shapes)
+    rows, mats, uvs = triangle_rows(shapes)
     v0, e1, e2 = rows[:, T_V0:T_V0 + 3], rows[:, T_E1:T_E1 + 3], rows[:, T_E2:T_E2 + 3]
     corners = np.stack([v0, v0 + e1, v0 + e2])
     lo, hi = corners.min(axis=0), corners.max(axis=0)
@@ -425,7 +523,29 @@ def mesh_table_entry(shapes, max_leaf=4) -> tuple:
     words = nodes_at + nodes.size
     head[[MH_MAGIC, MH_NTRI, MH_NMESH, MH_NNODES, MH_TRIS, MH_MATS, MH_NODES, MH_WORDS]] = (
         MAGIC, T, mats.shape[0], N, tris_at, mats_at, nodes_at, words)
-    table = np.concatenate([head, rows[order].ravel(), mats.ravel(), nodes.ravel()])
+    parts = [head, rows[order].ravel(), mats, nodes.ravel()]
+    if image:  # the UV part in the rows' leaf order, then one texel block per distinct image
+        head[MH_UVS] = words
+        parts.append(uvs[order].ravel())
+        words += uvs.size
+        head[MH_TEXELS] = words
+        blocks = {}
+        for i, mesh in enumerate(sh for sh in shapes if isinstance(sh, TriangleMesh)):
+            tex = mesh.shader.diffuse_color
+            if not _is_image(tex):
+                continue
+            t = _mesh_image(mesh, i)
+            digest = getattr(tex, "digest", None) or _texels_digest(t)
+            if digest not in blocks:
+                blocks[digest] = words
+                parts.append(t.ravel())
+                words += t.size
+            mats[i, L.M_TR] = blocks[digest]
+        if words >= 1 << 31:
+            raise ValueError(f"the mesh table would have {words} words; rtx_trace_mesh_uv takes fewer than 2^31")
+        head[MH_WORDS] = words
+    parts[2] = mats.ravel()
+    table = np.concatenate(parts)
     table.setflags(write=False)
     if len(_TABLES) >= 8:
         _TABLES.pop(next(iter(_TABLES)))
@@ -438,7 +558,9 @@ _TABLES: dict = {}  # (content digest, max_leaf) -> table
 
 def check_table(table) -> None:
     """ValueError unless ``table``'s header is that of a mesh table of its own length: the magic, the
-    counts and the three parts within it (what rtx_trace_mesh's kernel checks before it reads them)."""
+    counts and the three parts within it (what rtx_trace_mesh's kernel checks before it reads them), and,
+    where the header names a UV part or texel blocks (rtx_trace_mesh_uv), both of them and the block of
+    every image material within it."""
     from python_ray_tracer_amd.infrastructure.hip import _lib as L
 
     t = np.asarray(table)
@@ -450,3 +572,17 @@ def check_table(table) -> None:
           and c + N * L.NODE_WORDS <= w)
     if not ok:
         raise ValueError("mesh table: the header's counts and offsets do not fit the table")
+    u, x = t[MH_UVS], t[MH_TEXELS]
+    if u == 0 and x == 0:
+        return
+    ok = (u >= HDR_WORDS and u == np.floor(u) and u + T * UV_WORDS <= w and x >= HDR_WORDS and x == np.floor(x)
+          and x <= w)
+    if ok:
+        for m in t[b:b + M * L.MAT_WORDS].reshape(M, L.MAT_WORDS):
+            if m[L.M_TEX] == L.TEX_IMAGE:
+                off, W, H = m[L.M_TR], m[L.M_TG], m[L.M_TB]
+                ok = ok and (off >= x and off == np.floor(off) and W >= 1 and H >= 1 and W == np.floor(W)
+                             and H == np.floor(H) and W * H <= MAX_TEXELS and off + 3 * W * H <= w)
+    if not ok:
+        raise ValueError("mesh table: the offsets of the UV part, the texel blocks or an image material do not fit "
+                         "the table")

@@ -73,6 +73,10 @@ that device's current HIP stream and returns a new tensor):
   ``max_bounces`` in 0..16; origins, out_kind, workspace and ``check`` as ``rt::trace_lights``. With
   ``check=True`` the mesh table's header is read back and checked against its length too. Every tensor's
   dtype, device, contiguity and size is checked.
+* ``rt::trace_mesh_uv(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check=True)`` —
+  ``rt::trace_mesh`` on a table with texture coordinates and texel blocks (rtx_trace_mesh_uv; DESIGN.md §18):
+  the table ``meshes.mesh_table`` builds when a mesh has an ``ImageTexture``. With ``check=True`` the offsets
+  of the two new parts are checked against the table's length as well.
 * ``rt::env_sample(texels, gain, turn, dirs)``, ``rt::trace_lights_env(scene, n_spheres, lights, origins, dirs,
   max_bounces, out_kind, texels, gain, turn, check=True)`` and ``rt::trace_glass_env(scene, n_spheres, glass,
   origins, dirs, max_bounces, out_kind, texels, gain, turn, check=True)`` — the environment map (rtx_env_sample,
@@ -130,7 +134,7 @@ OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
        "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "trace_lights", "trace_mesh",
-       "env_sample",
+       "trace_mesh_uv", "env_sample",
        "trace_lights_env", "trace_glass_env", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
        "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)

@@ -34,7 +34,9 @@ Spec layout::
                 {"kind": "icosphere", "level": n} | {"kind": "torus", "R": .., "r": .., "nu": .., "nv": ..} |
                 {"kind": "triangles", "vertices": [V, 3], "faces": [F, 3], and optionally "normals": [V, 3]},
                 with "shader" as a sphere's and, all optional, "smooth": bool, "scale": s,
-                "translation": [x, y, z])
+                "translation": [x, y, z]; texture coordinates, for an image texture on the mesh
+                (textured_mesh_spec): "uvs": [F, 3, 2] or [V, 2] for kind "triangles", "uv": true for
+                "quad", "box" and "torus")
      "camera": {"position": [x, y, z], "width": W, "height": H}}
                 (with "target": [x, y, z] a domain.PerspectiveCamera; then also, all optional,
                  "up": [x, y, z], "fov": degrees, "lens_radius": r, "focus_distance": d)
@@ -145,28 +147,59 @@ def mesh_spec(width: int = 1920, height: int = 1080, level: int = 2) -> dict:
     return spec
 
 
-def mesh_arrays(m: dict):
-    """(vertices [V, 3], faces [F, 3], normals [V, 3] or None) of one entry of a spec's "meshes", placed
-    by its "scale" and "translation"."""
+def mesh_of(m: dict, shader=None):
+    """The ``TriangleMesh`` of one entry of a spec's "meshes", placed by its "scale" and "translation"."""
     from python_ray_tracer_amd import meshes
 
-    kind, smooth = m["kind"], bool(m.get("smooth", False))
+    kind, smooth, uv = m["kind"], bool(m.get("smooth", False)), bool(m.get("uv", False))
     if kind == "quad":
-        mesh = meshes.quad(m["corners"], None)
+        mesh = meshes.quad(m["corners"], shader, uv)
     elif kind == "box":
-        mesh = meshes.box(m["lo"], m["hi"], None)
+        mesh = meshes.box(m["lo"], m["hi"], shader, uv)
     elif kind == "icosphere":
-        mesh = meshes.icosphere(m["level"], None, smooth)
+        mesh = meshes.icosphere(m["level"], shader, smooth)
     elif kind == "torus":
-        mesh = meshes.torus(m["R"], m["r"], m["nu"], m["nv"], None, smooth)
+        mesh = meshes.torus(m["R"], m["r"], m["nu"], m["nv"], shader, smooth, uv)
     elif kind == "triangles":
-        mesh = meshes.TriangleMesh(m["vertices"], m["faces"], None, m.get("normals"))
+        mesh = meshes.TriangleMesh(m["vertices"], m["faces"], shader, m.get("normals"), m.get("uvs"))
     else:
         raise ValueError(f"unknown mesh kind {kind!r}")
     if smooth and mesh.normals is None:
         mesh.normals = meshes.vertex_normals(mesh.vertices, mesh.faces)
-    mesh = mesh.placed(m.get("scale", 1.0), m.get("translation", (0.0, 0.0, 0.0)))
+    return mesh.placed(m.get("scale", 1.0), m.get("translation", (0.0, 0.0, 0.0)))
+
+
+def mesh_arrays(m: dict):
+    """(vertices [V, 3], faces [F, 3], normals [V, 3] or None) of one entry of a spec's "meshes", placed
+    by its "scale" and "translation"."""
+    mesh = mesh_of(m)
     return mesh.vertices, mesh.faces, mesh.normals
+
+
+def uv_grid_texels(width: int = 64, height: int = 64) -> np.ndarray:
+    """A procedural texture as a float64 image (height, width, 3), so that nobody needs a file: red grows
+    with the column and green with the row from the bottom (so s and t can be read off a render), over a
+    grid of 8 x 8 cells whose every other cell is darker and whose blue tells the two kinds apart."""
+    w, h = int(width), int(height)
+    if w < 1 or h < 1:
+        raise ValueError(f"uv_grid_texels: width and height must be >= 1, got {width} x {height}")
+    s = ((np.arange(w) + 0.5) / w).reshape(1, w)
+    t = (1.0 - (np.arange(h) + 0.5) / h).reshape(h, 1)  # row 0 is the top of the image: t near 1
+    dark = ((np.floor(s * 8.0) + np.floor(t * 8.0)) % 2.0) == 1.0
+    shade = np.where(dark, 0.45, 1.0)
+    return np.stack([(0.15 + 0.85 * s) * shade, (0.15 + 0.85 * t) * shade, np.where(dark, 0.6, 0.2)], axis=-1)
+
+
+def textured_mesh_spec(width: int = 1920, height: int = 1080, level: int = 2, texels=None) -> dict:
+    """``mesh_spec`` with an image (``texels``, default ``uv_grid_texels()``) on its ground quad and on its
+    torus, both with texture coordinates ("uv": true): the textured frame of tools/meshuv_bench.py, the
+    README and the tests (``rtx_trace_mesh_uv``). The quad's 0..1 spans its 80 x 70 units once."""
+    spec = mesh_spec(width, height, level)
+    image = {"kind": "image", "texels": uv_grid_texels() if texels is None else texels}
+    for i in (0, 2):
+        spec["meshes"][i]["uv"] = True
+        spec["meshes"][i]["shader"] = {**spec["meshes"][i]["shader"], "texture": image}
+    return spec
 
 
 def sky_texels(width: int = 256, height: int = 128) -> np.ndarray:
@@ -295,8 +328,7 @@ CONFIGS = {
 
 def build_scene(spec: dict):
     """Instantiate ``spec`` with this package's HIP-backend classes."""
-    from python_ray_tracer_amd.domain import (Camera, ColoredPointLight, DomeLight, EnvironmentLight, PointLight, Scene3D,
-                                              TriangleMesh)
+    from python_ray_tracer_amd.domain import Camera, ColoredPointLight, DomeLight, EnvironmentLight, PointLight, Scene3D
     from python_ray_tracer_amd.infrastructure.hip import (
         HipRGBColor,
         HipShader,
@@ -324,8 +356,7 @@ def build_scene(spec: dict):
 
     shapes = [HipSphere(HipVector3D(*s["center"]), s["radius"], shader_of(s["shader"])) for s in spec["spheres"]]
     for m in spec.get("meshes", ()):  # optional: a mesh scene (mesh_spec)
-        vertices, faces, normals = mesh_arrays(m)
-        shapes.append(TriangleMesh(vertices, faces, shader_of(m["shader"]), normals))
+        shapes.append(mesh_of(m, shader_of(m["shader"])))
     lights = []
     for li in spec["lights"]:
         if li["kind"] == "point":
