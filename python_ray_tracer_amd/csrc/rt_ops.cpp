@@ -721,8 +721,34 @@ std::vector<at::Tensor> occlusion(const at::Tensor& scene, int64_t n_spheres, co
   return out;
 }
 
-// ---- transmission (rtx_trace_glass) ---------------------------------------------------------------
-// Shapes and ranges of rt::trace_glass's arguments, shared by the kernel and its Meta form: returns n.
+// ---- the kernels with a stack of pending rays: transmission (rtx_trace_glass), several point lights
+// (rtx_trace_lights), triangle meshes (rtx_trace_mesh, rtx_trace_mesh_uv), each also under an environment ----
+// Shapes and ranges of their arguments, shared by the kernels and their Meta forms.
+// dirs [3, n], origins [3] or [3, n], the bounce cap (0..cap: a `noun` scene needs one) and out_kind: returns n.
+int64_t check_rays_args(const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t cap,
+                        const char* noun, int64_t out_kind) {
+  TORCH_CHECK(dirs.scalar_type() == at::kDouble && dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be ", at::kDouble,
+              " [3, n], got ", dirs.scalar_type(), " ", dirs.sizes());
+  const int64_t n = dirs.size(1);
+  TORCH_CHECK(origins.scalar_type() == at::kDouble &&
+                  ((origins.dim() == 1 && origins.numel() == 3) ||
+                   (origins.dim() == 2 && origins.size(0) == 3 && origins.size(1) == n)),
+              "origins must be ", at::kDouble, " [3] (shared) or [3, n] with n = ", n, ", got ", origins.scalar_type(),
+              " ", origins.sizes());
+  TORCH_CHECK(max_bounces >= 0 && max_bounces <= cap, "max_bounces must lie in 0..", (int)cap, " (a ", noun,
+              " scene needs a finite cap), got ", max_bounces);
+  TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA || out_kind == RTX_OUT_U8_HWC,
+              "bad out_kind ", out_kind);
+  return n;
+}
+
+void check_lights_table(const at::Tensor& lights) {
+  TORCH_CHECK(lights.scalar_type() == at::kDouble && lights.dim() == 2 && lights.size(1) == 6 &&
+                  lights.size(0) >= 1 && lights.size(0) <= RTX_MAX_POINT_LIGHTS,
+              "lights must be ", at::kDouble, " [L, 6] with L in 1..", (int)RTX_MAX_POINT_LIGHTS,
+              " (lights.lights_table), got ", lights.scalar_type(), " ", lights.sizes());
+}
+
 int64_t check_glass(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass, const at::Tensor& origins,
                     const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind) {
   check_scene_shape(scene, n_spheres);
@@ -730,103 +756,16 @@ int64_t check_glass(const at::Tensor& scene, int64_t n_spheres, const at::Tensor
                   glass.size(1) == n_spheres,
               "glass must be ", at::kDouble, " [2, n_spheres] (glass.glass_table), got ", glass.scalar_type(), " ",
               glass.sizes());
-  TORCH_CHECK(dirs.scalar_type() == at::kDouble && dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be ", at::kDouble,
-              " [3, n], got ", dirs.scalar_type(), " ", dirs.sizes());
-  const int64_t n = dirs.size(1);
-  TORCH_CHECK(origins.scalar_type() == at::kDouble &&
-                  ((origins.dim() == 1 && origins.numel() == 3) ||
-                   (origins.dim() == 2 && origins.size(0) == 3 && origins.size(1) == n)),
-              "origins must be ", at::kDouble, " [3] (shared) or [3, n] with n = ", n, ", got ", origins.scalar_type(),
-              " ", origins.sizes());
-  TORCH_CHECK(max_bounces >= 0 && max_bounces <= RTX_GLASS_MAX_BOUNCES, "max_bounces must lie in 0..",
-              (int)RTX_GLASS_MAX_BOUNCES, " (a transmissive scene needs a finite cap), got ", max_bounces);
-  TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA || out_kind == RTX_OUT_U8_HWC,
-              "bad out_kind ", out_kind);
-  return n;
+  return check_rays_args(origins, dirs, max_bounces, RTX_GLASS_MAX_BOUNCES, "transmissive", out_kind);
 }
 
-at::Tensor trace_glass(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass, const at::Tensor& origins,
-                       const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind, bool check) {
-  check_gpu(scene, "scene", at::kDouble);
-  const at::OptionalDeviceGuard guard(at::device_of(scene));
-  const struct { const at::Tensor& t; const char* name; } in[] = {{glass, "glass"}, {origins, "origins"}, {dirs, "dirs"}};
-  for (const auto& a : in) {
-    check_gpu(a.t, a.name, at::kDouble);
-    check_same_device(scene, a.t, a.name);
-  }
-  const int64_t n = check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind);
-  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
-  if (check) check_headers(scene, n_spheres);
-  if (n == 0) return out;  // (an empty tensor's pointer may be null)
-  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
-  at::Tensor ws = at::zeros({(int64_t)rtx_glass_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
-  check_rc(rtx_trace_glass(scene.data_ptr<double>(), (int)n_spheres, glass.data_ptr<double>(),
-                           origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
-                           (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(),
-                           stream_of(scene)),
-           "rtx_trace_glass");
-  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
-    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
-    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
-                4 * max_bounces + 4, " pending rays; HipRenderer raises RecursionError)");
-  }
-  return out;
-}
-
-// ---- several point lights (rtx_trace_lights) ------------------------------------------------------
-// Shapes and ranges of rt::trace_lights's arguments, shared by the kernel and its Meta form: returns n.
 int64_t check_lights(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights, const at::Tensor& origins,
                      const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind) {
   check_scene_shape(scene, n_spheres);
-  TORCH_CHECK(lights.scalar_type() == at::kDouble && lights.dim() == 2 && lights.size(1) == 6 &&
-                  lights.size(0) >= 1 && lights.size(0) <= RTX_MAX_POINT_LIGHTS,
-              "lights must be ", at::kDouble, " [L, 6] with L in 1..", (int)RTX_MAX_POINT_LIGHTS,
-              " (lights.lights_table), got ", lights.scalar_type(), " ", lights.sizes());
-  TORCH_CHECK(dirs.scalar_type() == at::kDouble && dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be ", at::kDouble,
-              " [3, n], got ", dirs.scalar_type(), " ", dirs.sizes());
-  const int64_t n = dirs.size(1);
-  TORCH_CHECK(origins.scalar_type() == at::kDouble &&
-                  ((origins.dim() == 1 && origins.numel() == 3) ||
-                   (origins.dim() == 2 && origins.size(0) == 3 && origins.size(1) == n)),
-              "origins must be ", at::kDouble, " [3] (shared) or [3, n] with n = ", n, ", got ", origins.scalar_type(),
-              " ", origins.sizes());
-  TORCH_CHECK(max_bounces >= 0 && max_bounces <= RTX_LIGHTS_MAX_BOUNCES, "max_bounces must lie in 0..",
-              (int)RTX_LIGHTS_MAX_BOUNCES, " (a multi-light scene needs a finite cap), got ", max_bounces);
-  TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA || out_kind == RTX_OUT_U8_HWC,
-              "bad out_kind ", out_kind);
-  return n;
+  check_lights_table(lights);
+  return check_rays_args(origins, dirs, max_bounces, RTX_LIGHTS_MAX_BOUNCES, "multi-light", out_kind);
 }
 
-at::Tensor trace_lights(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights, const at::Tensor& origins,
-                        const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind, bool check) {
-  check_gpu(scene, "scene", at::kDouble);
-  const at::OptionalDeviceGuard guard(at::device_of(scene));
-  const struct { const at::Tensor& t; const char* name; } in[] = {{lights, "lights"}, {origins, "origins"}, {dirs, "dirs"}};
-  for (const auto& a : in) {
-    check_gpu(a.t, a.name, at::kDouble);
-    check_same_device(scene, a.t, a.name);
-  }
-  const int64_t n = check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind);
-  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
-  if (check) check_headers(scene, n_spheres);
-  if (n == 0) return out;  // (an empty tensor's pointer may be null)
-  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
-  at::Tensor ws = at::zeros({(int64_t)rtx_lights_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
-  check_rc(rtx_trace_lights(scene.data_ptr<double>(), (int)n_spheres, lights.data_ptr<double>(), (int)lights.size(0),
-                            origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
-                            (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(),
-                            stream_of(scene)),
-           "rtx_trace_lights");
-  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
-    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
-    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
-                2 * max_bounces + 2, " pending rays; HipRenderer raises RecursionError)");
-  }
-  return out;
-}
-
-// ---- triangle meshes (rtx_trace_mesh) -------------------------------------------------------------
-// Shapes and ranges of rt::trace_mesh's arguments, shared by the kernel and its Meta form: returns n.
 int64_t check_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
                    const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind) {
   TORCH_CHECK(scene.dim() == 1, "scene must be the 1-D packed blob (scene_pack.pack_scene)");
@@ -837,23 +776,8 @@ int64_t check_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor&
                   mesh.numel() <= INT32_MAX,
               "mesh must be ", at::kDouble, " [words] with at least ", (int)RTX_MESH_HDR_WORDS,
               " words (meshes.mesh_table), got ", mesh.scalar_type(), " ", mesh.sizes());
-  TORCH_CHECK(lights.scalar_type() == at::kDouble && lights.dim() == 2 && lights.size(1) == 6 &&
-                  lights.size(0) >= 1 && lights.size(0) <= RTX_MAX_POINT_LIGHTS,
-              "lights must be ", at::kDouble, " [L, 6] with L in 1..", (int)RTX_MAX_POINT_LIGHTS,
-              " (lights.lights_table), got ", lights.scalar_type(), " ", lights.sizes());
-  TORCH_CHECK(dirs.scalar_type() == at::kDouble && dirs.dim() == 2 && dirs.size(0) == 3, "dirs must be ", at::kDouble,
-              " [3, n], got ", dirs.scalar_type(), " ", dirs.sizes());
-  const int64_t n = dirs.size(1);
-  TORCH_CHECK(origins.scalar_type() == at::kDouble &&
-                  ((origins.dim() == 1 && origins.numel() == 3) ||
-                   (origins.dim() == 2 && origins.size(0) == 3 && origins.size(1) == n)),
-              "origins must be ", at::kDouble, " [3] (shared) or [3, n] with n = ", n, ", got ", origins.scalar_type(),
-              " ", origins.sizes());
-  TORCH_CHECK(max_bounces >= 0 && max_bounces <= RTX_MESH_MAX_BOUNCES, "max_bounces must lie in 0..",
-              (int)RTX_MESH_MAX_BOUNCES, " (a mesh scene needs a finite cap), got ", max_bounces);
-  TORCH_CHECK(out_kind == RTX_OUT_F32_SOA || out_kind == RTX_OUT_F64_SOA || out_kind == RTX_OUT_U8_HWC,
-              "bad out_kind ", out_kind);
-  return n;
+  check_lights_table(lights);
+  return check_rays_args(origins, dirs, max_bounces, RTX_MESH_MAX_BOUNCES, "mesh", out_kind);
 }
 
 // The mesh table's header against its length: the host-side form of the kernel's own test, which reads a
@@ -874,53 +798,6 @@ void check_mesh_header(const at::Tensor& mesh, bool uv = false) {
                 "mesh table: the offsets of the UV part and the texel blocks do not fit its ", mesh.numel(),
                 " words (a table of meshes.mesh_table with an ImageTexture on a mesh)");
   }
-}
-
-// rt::trace_mesh (uv false) and rt::trace_mesh_uv
-at::Tensor trace_mesh_call(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
-                           const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
-                           bool check, bool uv) {
-  check_gpu(scene, "scene", at::kDouble);
-  const at::OptionalDeviceGuard guard(at::device_of(scene));
-  const struct { const at::Tensor& t; const char* name; } in[] = {
-      {mesh, "mesh"}, {lights, "lights"}, {origins, "origins"}, {dirs, "dirs"}};
-  for (const auto& a : in) {
-    check_gpu(a.t, a.name, at::kDouble);
-    check_same_device(scene, a.t, a.name);
-  }
-  const int64_t n = check_mesh(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind);
-  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
-  if (check) {
-    check_headers(scene, n_spheres);
-    check_mesh_header(mesh, uv);
-  }
-  if (n == 0) return out;  // (an empty tensor's pointer may be null)
-  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
-  at::Tensor ws = at::zeros({(int64_t)rtx_mesh_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
-  check_rc((uv ? rtx_trace_mesh_uv : rtx_trace_mesh)(
-               scene.data_ptr<double>(), (int)n_spheres, mesh.data_ptr<double>(), mesh.numel(),
-               lights.data_ptr<double>(), (int)lights.size(0), origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n,
-               dirs.data_ptr<double>(), n, (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(),
-               (size_t)ws.numel(), stream_of(scene)),
-           uv ? "rtx_trace_mesh_uv" : "rtx_trace_mesh");
-  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
-    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
-    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
-                2 * max_bounces + 2, " pending rays; HipRenderer raises RecursionError)");
-  }
-  return out;
-}
-
-at::Tensor trace_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
-                      const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
-                      bool check) {
-  return trace_mesh_call(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check, false);
-}
-
-at::Tensor trace_mesh_uv(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
-                         const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
-                         bool check) {
-  return trace_mesh_call(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check, true);
 }
 
 // ---- the environment map (rtx_env_sample, rtx_trace_lights_env, rtx_trace_glass_env) ----------------
@@ -962,72 +839,159 @@ at::Tensor env_sample(const at::Tensor& texels, c10::ArrayRef<double> gain, doub
   return out;
 }
 
-at::Tensor trace_lights_env(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights,
-                            const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
-                            const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, bool check) {
+// ---- the ops of the kernels with a stack of pending rays ------------------------------------------------
+struct NamedTensor {
+  const at::Tensor& t;
+  const char* name;
+};
+
+struct EnvArg {  // an op's environment arguments, and the struct the op's body fills from them
+  const at::Tensor& texels;
+  c10::ArrayRef<double> gain;
+  double turn;
+  rtx_env_t env;
+};
+
+struct StackOp {  // what one of these ops is, beside its arguments
+  const char* entry;                    // the library's entry, for the error message
+  size_t (*ws_bytes)(int64_t, int);     // its workspace size function
+  int64_t depth;                        // the pending rays a lane's stack holds, for the overflow message
+  const at::Tensor* mesh = nullptr;     // the mesh table whose header is checked with the blob's, if any
+  bool uv = false;                      // ... with its UV part
+};
+
+// The body of rt::trace_glass, trace_lights, trace_mesh, trace_mesh_uv, trace_lights_env and trace_glass_env: the
+// device guard and the device checks of the float64 inputs `in` (and the environment's texels), `shape()` (the
+// op's check_*: returns n), the output, the headers, the op's own zeroed workspace, `call(n, out, ws)` (the
+// library's entry) and the status.
+template <class Shape, class Call>
+at::Tensor trace_stack_rays(const StackOp& op, const at::Tensor& scene, int64_t n_spheres,
+                            std::initializer_list<NamedTensor> in, Shape&& shape, Call&& call, int64_t max_bounces,
+                            int64_t out_kind, bool check, EnvArg* e = nullptr) {
   check_gpu(scene, "scene", at::kDouble);
   const at::OptionalDeviceGuard guard(at::device_of(scene));
-  const struct { const at::Tensor& t; const char* name; } in[] = {{lights, "lights"}, {origins, "origins"}, {dirs, "dirs"}};
   for (const auto& a : in) {
     check_gpu(a.t, a.name, at::kDouble);
     check_same_device(scene, a.t, a.name);
   }
-  check_gpu(texels, "texels", at::kFloat);
-  check_same_device(scene, texels, "texels");
-  const int64_t n = check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind);
-  rtx_env_t env;
-  check_env(texels, gain, turn, env);
+  if (e) {
+    check_gpu(e->texels, "texels", at::kFloat);
+    check_same_device(scene, e->texels, "texels");
+  }
+  const int64_t n = shape();
+  if (e) check_env(e->texels, e->gain, e->turn, e->env);
   at::Tensor out = new_output(scene, n, -1, 0, out_kind);
-  if (check) check_headers(scene, n_spheres);
+  if (check) {
+    check_headers(scene, n_spheres);
+    if (op.mesh) check_mesh_header(*op.mesh, op.uv);
+  }
   if (n == 0) return out;  // (an empty tensor's pointer may be null)
-  env.texels = texels.data_ptr<float>();
+  if (e) e->env.texels = e->texels.data_ptr<float>();
   // the op's own workspace: the zeroed header and the workers' stacks of pending rays
-  at::Tensor ws = at::zeros({(int64_t)rtx_lights_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
-  check_rc(rtx_trace_lights_env(scene.data_ptr<double>(), (int)n_spheres, lights.data_ptr<double>(), (int)lights.size(0),
-                                origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
-                                (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(),
-                                stream_of(scene), &env),
-           "rtx_trace_lights_env");
+  at::Tensor ws = at::zeros({(int64_t)op.ws_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
+  check_rc(call(n, out, ws), op.entry);
   if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
     const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
     TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
-                2 * max_bounces + 2, " pending rays; HipRenderer raises RecursionError)");
+                op.depth, " pending rays; HipRenderer raises RecursionError)");
   }
   return out;
+}
+
+// rt::trace_glass (e null) and rt::trace_glass_env
+at::Tensor trace_glass_under(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass,
+                             const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                             bool check, EnvArg* e) {
+  const StackOp op{e ? "rtx_trace_glass_env" : "rtx_trace_glass", rtx_glass_workspace_bytes, 4 * max_bounces + 4};
+  return trace_stack_rays(
+      op, scene, n_spheres, {{glass, "glass"}, {origins, "origins"}, {dirs, "dirs"}},
+      [&] { return check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind); },
+      [&](int64_t n, at::Tensor& out, at::Tensor& ws) {
+        const double *S = scene.data_ptr<double>(), *G = glass.data_ptr<double>(), *O = origins.data_ptr<double>(),
+                     *D = dirs.data_ptr<double>();
+        const int64_t stride = origins.dim() == 1 ? 0 : n;
+        if (e)
+          return rtx_trace_glass_env(S, (int)n_spheres, G, O, stride, D, n, (int)max_bounces, out.data_ptr(),
+                                     (int)out_kind, ws.data_ptr(), (size_t)ws.numel(), stream_of(scene), &e->env);
+        return rtx_trace_glass(S, (int)n_spheres, G, O, stride, D, n, (int)max_bounces, out.data_ptr(), (int)out_kind,
+                               ws.data_ptr(), (size_t)ws.numel(), stream_of(scene));
+      },
+      max_bounces, out_kind, check, e);
+}
+
+// rt::trace_lights (e null) and rt::trace_lights_env
+at::Tensor trace_lights_under(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights,
+                              const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                              bool check, EnvArg* e) {
+  const StackOp op{e ? "rtx_trace_lights_env" : "rtx_trace_lights", rtx_lights_workspace_bytes, 2 * max_bounces + 2};
+  return trace_stack_rays(
+      op, scene, n_spheres, {{lights, "lights"}, {origins, "origins"}, {dirs, "dirs"}},
+      [&] { return check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind); },
+      [&](int64_t n, at::Tensor& out, at::Tensor& ws) {
+        const double *S = scene.data_ptr<double>(), *T = lights.data_ptr<double>(), *O = origins.data_ptr<double>(),
+                     *D = dirs.data_ptr<double>();
+        const int64_t stride = origins.dim() == 1 ? 0 : n;
+        const int L = (int)lights.size(0);
+        if (e)
+          return rtx_trace_lights_env(S, (int)n_spheres, T, L, O, stride, D, n, (int)max_bounces, out.data_ptr(),
+                                      (int)out_kind, ws.data_ptr(), (size_t)ws.numel(), stream_of(scene), &e->env);
+        return rtx_trace_lights(S, (int)n_spheres, T, L, O, stride, D, n, (int)max_bounces, out.data_ptr(),
+                                (int)out_kind, ws.data_ptr(), (size_t)ws.numel(), stream_of(scene));
+      },
+      max_bounces, out_kind, check, e);
+}
+
+// rt::trace_mesh (uv false) and rt::trace_mesh_uv
+at::Tensor trace_mesh_call(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                           const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                           bool check, bool uv) {
+  const StackOp op{uv ? "rtx_trace_mesh_uv" : "rtx_trace_mesh", rtx_mesh_workspace_bytes, 2 * max_bounces + 2, &mesh, uv};
+  return trace_stack_rays(
+      op, scene, n_spheres, {{mesh, "mesh"}, {lights, "lights"}, {origins, "origins"}, {dirs, "dirs"}},
+      [&] { return check_mesh(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind); },
+      [&](int64_t n, at::Tensor& out, at::Tensor& ws) {
+        return (uv ? rtx_trace_mesh_uv : rtx_trace_mesh)(
+            scene.data_ptr<double>(), (int)n_spheres, mesh.data_ptr<double>(), mesh.numel(), lights.data_ptr<double>(),
+            (int)lights.size(0), origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
+            (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(), stream_of(scene));
+      },
+      max_bounces, out_kind, check);
+}
+
+at::Tensor trace_glass(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass, const at::Tensor& origins,
+                       const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind, bool check) {
+  return trace_glass_under(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind, check, nullptr);
+}
+
+at::Tensor trace_lights(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights, const at::Tensor& origins,
+                        const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind, bool check) {
+  return trace_lights_under(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind, check, nullptr);
+}
+
+at::Tensor trace_mesh(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                      const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                      bool check) {
+  return trace_mesh_call(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check, false);
+}
+
+at::Tensor trace_mesh_uv(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                         const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                         bool check) {
+  return trace_mesh_call(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check, true);
+}
+
+at::Tensor trace_lights_env(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights,
+                            const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
+                            const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, bool check) {
+  EnvArg e{texels, gain, turn, {}};
+  return trace_lights_under(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind, check, &e);
 }
 
 at::Tensor trace_glass_env(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass,
                            const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
                            const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, bool check) {
-  check_gpu(scene, "scene", at::kDouble);
-  const at::OptionalDeviceGuard guard(at::device_of(scene));
-  const struct { const at::Tensor& t; const char* name; } in[] = {{glass, "glass"}, {origins, "origins"}, {dirs, "dirs"}};
-  for (const auto& a : in) {
-    check_gpu(a.t, a.name, at::kDouble);
-    check_same_device(scene, a.t, a.name);
-  }
-  check_gpu(texels, "texels", at::kFloat);
-  check_same_device(scene, texels, "texels");
-  const int64_t n = check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind);
-  rtx_env_t env;
-  check_env(texels, gain, turn, env);
-  at::Tensor out = new_output(scene, n, -1, 0, out_kind);
-  if (check) check_headers(scene, n_spheres);
-  if (n == 0) return out;  // (an empty tensor's pointer may be null)
-  env.texels = texels.data_ptr<float>();
-  // the op's own workspace: the zeroed header and the workers' stacks of pending rays
-  at::Tensor ws = at::zeros({(int64_t)rtx_glass_workspace_bytes(n, (int)max_bounces)}, scene.options().dtype(at::kByte));
-  check_rc(rtx_trace_glass_env(scene.data_ptr<double>(), (int)n_spheres, glass.data_ptr<double>(),
-                               origins.data_ptr<double>(), origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n,
-                               (int)max_bounces, out.data_ptr(), (int)out_kind, ws.data_ptr(), (size_t)ws.numel(),
-                               stream_of(scene), &env),
-           "rtx_trace_glass_env");
-  if (check) {  // (a synchronisation; check=False leaves an overflowed lane's dropped rays unreported)
-    const int32_t st = ws.narrow(0, 4 * RTX_WS_STATUS, 4).view(at::kInt).item<int32_t>();
-    TORCH_CHECK(!(st & RTX_ST_STACK_OVERFLOW), "maximum recursion depth exceeded (a ray tree with ties needed more than ",
-                4 * max_bounces + 4, " pending rays; HipRenderer raises RecursionError)");
-  }
-  return out;
+  EnvArg e{texels, gain, turn, {}};
+  return trace_glass_under(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind, check, &e);
 }
 
 int64_t status(at::Tensor& workspace) {
@@ -1240,19 +1204,19 @@ at::Tensor env_sample_meta(const at::Tensor& texels, c10::ArrayRef<double> gain,
 at::Tensor trace_lights_env_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights,
                                  const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces,
                                  int64_t out_kind, const at::Tensor& texels, c10::ArrayRef<double> gain, double turn,
-                                 bool) {
+                                 bool check) {
   rtx_env_t env;
   check_env(texels, gain, turn, env);
-  return new_output(scene, check_lights(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
+  return trace_lights_meta(scene, n_spheres, lights, origins, dirs, max_bounces, out_kind, check);
 }
 
 at::Tensor trace_glass_env_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& glass,
                                 const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces,
                                 int64_t out_kind, const at::Tensor& texels, c10::ArrayRef<double> gain, double turn,
-                                bool) {
+                                bool check) {
   rtx_env_t env;
   check_env(texels, gain, turn, env);
-  return new_output(scene, check_glass(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind), -1, 0, out_kind);
+  return trace_glass_meta(scene, n_spheres, glass, origins, dirs, max_bounces, out_kind, check);
 }
 
 at::Tensor edge_mask_meta(const at::Tensor& color, const at::Tensor& id, const at::Tensor& hits,

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
 
 #include "../../include/rtx_hip.h"
 
@@ -93,6 +94,54 @@ void ray_params(P& p, const double* scene, int n_spheres, int mode, const double
   p.org_stride = origin_stride;
   p.dir = dirs;
   p.n = n;
+}
+
+// What the launchers of the kernels with a stack of pending rays check alike (rtx_trace_glass, rtx_trace_lights,
+// rtx_trace_mesh and their _env and _uv forms), in the two halves that stand before and after a launcher's own
+// range checks (sphere and table counts, the bounce cap), so that every entry fails first where it did: RTX_OK, or
+// the code rtx_fail returned. `tables`: the launcher's side tables, each with its message for a null pointer.
+struct StackTable {
+  const void* ptr;
+  const char* null_message;
+};
+inline int stack_call_pointers(const void* scene, std::initializer_list<StackTable> tables, const void* origins,
+                               const void* dirs, const void* out, const void* workspace) {
+  if (!scene) return rtx_fail(RTX_E_ARG, "null scene pointer");
+  for (const StackTable& t : tables)
+    if (!t.ptr) return rtx_fail(RTX_E_ARG, "%s", t.null_message);
+  if (!origins || !dirs) return rtx_fail(RTX_E_ARG, "null ray pointer (origins, dirs)");
+  if (!out) return rtx_fail(RTX_E_ARG, "null output pointer");
+  if (!workspace) return rtx_fail(RTX_E_ARG, "null workspace pointer");
+  return RTX_OK;
+}
+// `need`: the bytes the launcher's size function (`size_fn`, named in the message) asks for n rays.
+inline int stack_call_rays(int out_kind, int64_t n, int64_t origin_stride, size_t workspace_bytes, size_t need,
+                           const char* size_fn) {
+  if (out_kind != RTX_OUT_F32_SOA && out_kind != RTX_OUT_F64_SOA && out_kind != RTX_OUT_U8_HWC)
+    return rtx_fail(RTX_E_ARG, "bad out_kind %d", out_kind);
+  if (n < 0) return rtx_fail(RTX_E_ARG, "negative ray count");
+  if (origin_stride != 0 && origin_stride != n)
+    return rtx_fail(RTX_E_ARG, "origin_stride must be 0 (a shared origin) or n");
+  if (workspace_bytes < need)
+    return rtx_fail(RTX_E_WORKSPACE, "workspace too small: %zu < %zu bytes (%s)", workspace_bytes, need, size_fn);
+  return RTX_OK;
+}
+
+// The ray, output, status and stack fields that the Params of those kernels share (GlassParams, LightsParams,
+// MeshParams), over a workspace that passed stack_call_rays. p is value-initialised by the caller.
+template <typename P>
+void stack_params(P& p, const double* origins, int64_t origin_stride, const double* dirs, int64_t n, int max_bounces,
+                  void* out, int out_kind, void* workspace, int64_t n_workers) {
+  p.org = origins;
+  p.org_stride = origin_stride;
+  p.dir = dirs;
+  p.n = n;
+  p.max_bounces = max_bounces;
+  p.out = out;
+  p.out_kind = out_kind;
+  p.status = (uint32_t*)workspace + RTX_WS_STATUS;
+  p.stack = (double*)((uint8_t*)workspace + RTX_WS_HDR_BYTES);
+  p.n_workers = n_workers;
 }
 
 }  // namespace

@@ -278,12 +278,9 @@ int trace_mesh_call(const double* scene, int n_spheres, const double* mesh, int6
                     int n_lights, const double* origins, int64_t origin_stride, const double* dirs, int64_t n,
                     int max_bounces, void* out, int out_kind, void* workspace, size_t workspace_bytes, void* stream,
                     bool uv) {
-  if (!scene) return rtx_fail(RTX_E_ARG, "null scene pointer");
-  if (!mesh) return rtx_fail(RTX_E_ARG, "null mesh table pointer");
-  if (!lights) return rtx_fail(RTX_E_ARG, "null lights table pointer");
-  if (!origins || !dirs) return rtx_fail(RTX_E_ARG, "null ray pointer (origins, dirs)");
-  if (!out) return rtx_fail(RTX_E_ARG, "null output pointer");
-  if (!workspace) return rtx_fail(RTX_E_ARG, "null workspace pointer");
+  if (const int rc = stack_call_pointers(scene, {{mesh, "null mesh table pointer"}, {lights, "null lights table pointer"}},
+                                         origins, dirs, out, workspace))
+    return rc;
   if (n_spheres < 0 || n_spheres > RTX_MAX_SPHERES) return rtx_fail(RTX_E_ARG, "n_spheres out of range");
   if (mesh_words < RTX_MESH_HDR_WORDS || mesh_words > INT32_MAX)
     return rtx_fail(RTX_E_ARG, "mesh_words out of range (%d..2^31 - 1)", (int)RTX_MESH_HDR_WORDS);
@@ -292,15 +289,10 @@ int trace_mesh_call(const double* scene, int n_spheres, const double* mesh, int6
   if (max_bounces < 0 || max_bounces > RTX_MESH_MAX_BOUNCES)
     return rtx_fail(RTX_E_ARG, "max_bounces out of range (0..%d): a mesh scene needs a finite cap",
                     (int)RTX_MESH_MAX_BOUNCES);
-  if (out_kind != RTX_OUT_F32_SOA && out_kind != RTX_OUT_F64_SOA && out_kind != RTX_OUT_U8_HWC)
-    return rtx_fail(RTX_E_ARG, "bad out_kind %d", out_kind);
-  if (n < 0) return rtx_fail(RTX_E_ARG, "negative ray count");
-  if (origin_stride != 0 && origin_stride != n)
-    return rtx_fail(RTX_E_ARG, "origin_stride must be 0 (a shared origin) or n");
-  const size_t need = rtx_mesh_workspace_bytes(n, max_bounces);
-  if (workspace_bytes < need)
-    return rtx_fail(RTX_E_WORKSPACE, "workspace too small: %zu < %zu bytes (rtx_mesh_workspace_bytes)",
-                    workspace_bytes, need);
+  // (the size is computed ahead of the checks on out_kind and n: the size function has no effects and gives 0 for n < 0)
+  if (const int rc = stack_call_rays(out_kind, n, origin_stride, workspace_bytes,
+                                     rtx_mesh_workspace_bytes(n, max_bounces), "rtx_mesh_workspace_bytes"))
+    return rc;
   if (n == 0) return RTX_OK;
   MeshParams p{};
   p.scene = scene;
@@ -309,16 +301,7 @@ int trace_mesh_call(const double* scene, int n_spheres, const double* mesh, int6
   p.mesh_words = mesh_words;
   p.lights = lights;
   p.n_lights = n_lights;
-  p.org = origins;
-  p.org_stride = origin_stride;
-  p.dir = dirs;
-  p.n = n;
-  p.max_bounces = max_bounces;
-  p.out = out;
-  p.out_kind = out_kind;
-  p.status = (uint32_t*)workspace + RTX_WS_STATUS;
-  p.stack = (double*)((uint8_t*)workspace + RTX_WS_HDR_BYTES);
-  p.n_workers = mesh_workers(n, max_bounces);
+  stack_params(p, origins, origin_stride, dirs, n, max_bounces, out, out_kind, workspace, mesh_workers(n, max_bounces));
   const dim3 grid((unsigned)(p.n_workers / 64));
   if (uv) {
     hipLaunchKernelGGL(k_trace_mesh_uv, grid, dim3(64), 0, (hipStream_t)stream, p);

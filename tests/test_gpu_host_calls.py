@@ -4,7 +4,8 @@ Parity tests compare pixels; they cannot see a dropped RTX_F_NO_GENERAL, a probe
 that is no longer passed, an extra launch or another workspace size: the frame is the same and only
 the time per step moves. Here the renderer's ``_lib`` is replaced by a proxy that forwards every call
 and logs its name and arguments, a fixed script runs on the README scene at 16 x 8 (two 16 x 4 wave
-tiles: the smallest frame with more than one dispatch unit), and the log must equal
+tiles: the smallest frame with more than one dispatch unit) and, at its end, on the scenes that are traced
+with a side table (glass, several lights, an environment, meshes), and the log must equal
 tests/golden/host_calls.json. Integers and floats are logged as they are; whatever the entry point
 declares as a pointer (a ``data_ptr()``, an address, a stream, a ctypes object) as 0 or 1 for null or
 not. The device is synchronised after every step, so every probe event has landed before the next
@@ -129,6 +130,31 @@ def _run_script(hip) -> list:
 
     rs = renderer(3, collect_stats=True)
     step("collect_stats render_tile", lambda: rs.render_tile(scene))
+
+    # the side-table scenes (glass, lights, environment, mesh): each twice, the second skips the status read-back
+    glassy_env = scenes.env_spec(W, H, 8, 4)
+    glassy_env["spheres"][1]["shader"].update(transmission_gain=0.9, diffuse_gain=0.1)
+    tabled = {
+        "glass": scenes.glass_spec(W, H),
+        "lights": scenes.lights_spec(W, H),
+        "env": scenes.env_spec(W, H, 8, 4),
+        "glass env": glassy_env,
+        "mesh": scenes.mesh_spec(W, H, 1),
+        "mesh uv": scenes.textured_mesh_spec(W, H, 1, scenes.uv_grid_texels(4, 4)),
+    }
+    tabled = {name: scenes.build_scene(s) for name, s in tabled.items()}
+    rt = renderer(3)
+    for name, sc in tabled.items():
+        for i in range(2):
+            step(f"{name} render_tile {i}", lambda: rt.render_tile(sc))
+    step("lights row tile", lambda: rt.render_tile(tabled["lights"], 4, 2, 1))
+    mesh = tabled["mesh"]
+    mesh_rays = rt.get_ray_directions(mesh.camera)
+    step("mesh materialise", lambda: mesh_rays.data)
+    step("mesh raytrace_scene materialised", lambda: rt.raytrace_scene(mesh.camera.position, mesh_rays, mesh))
+    rt2 = renderer(3, samples=2)
+    step("samples=2 glass render_tile", lambda: rt2.render_tile(tabled["glass"]))
+    step("samples=2 mesh render_tile", lambda: rt2.render_tile(mesh))
     return log
 
 

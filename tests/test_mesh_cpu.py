@@ -684,44 +684,83 @@ def test_every_refusal_of_the_renderer_comes_before_any_gpu_use(monkeypatch):
     assert r._mesh_table(plain, "render") is None
 
 
-def test_an_overflowed_stack_raises_recursion_error(monkeypatch):
-    """The status word's host handling, without a kernel: _trace_mesh reads it once, raises RecursionError for
-    the overflow flag and clears it; a clean render of a key is remembered and not read back again."""
+class _CountingWorkspace(torch.Tensor):
+    """A CPU workspace that counts the reads of its header (``ws[:8]``: the status word's read-back)."""
+
+    reads = 0
+
+    def __getitem__(self, index):
+        if index == slice(None, 8):
+            type(self).reads += 1
+        return super().__getitem__(index)
+
+
+_STACK_ROUTES = {  # route -> (library entry, the clean-key record of its kernel, pending rays at max_bounces=3)
+    "glass": ("rtx_trace_glass", "_glass_clean", 16),
+    "lights": ("rtx_trace_lights", "_lights_clean", 8),
+    "env_lights": ("rtx_trace_lights_env", "_lights_clean", 8),
+    "env_glass": ("rtx_trace_glass_env", "_glass_clean", 16),
+    "mesh": ("rtx_trace_mesh", "_mesh_clean", 8),
+    "mesh_uv": ("rtx_trace_mesh_uv", "_mesh_clean", 8),
+}
+
+
+@pytest.mark.parametrize("route", sorted(_STACK_ROUTES))
+def test_an_overflowed_stack_raises_recursion_error(monkeypatch, route):
+    """The status word's host handling, without a kernel, on every route to a kernel with a stack of pending
+    rays: the trace method reads the status once, raises RecursionError for the overflow flag (4 B + 4 pending
+    rays for the glass kernels, 2 B + 2 for the others) and clears it; a clean render of a key is remembered, in
+    the record of the kernel underneath, and not read back again; a failed one is not remembered."""
     from python_ray_tracer_amd.infrastructure.hip import HipRenderer, base
 
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    calls, reads = [], []
+    entry, record, pending = _STACK_ROUTES[route]
+    calls = []
 
     class Lib:
-        def rtx_mesh_workspace_bytes(self, n, B):
-            return 64
+        def __getattr__(self, name):
+            if name.endswith("_workspace_bytes"):
+                return lambda n, B: 64
 
-        def rtx_trace_mesh(self, *a):
-            calls.append(a)
-            return 0
+            def call(*a):
+                calls.append(name)
+                return 0
+
+            return call
+
+    class Workspace(_CountingWorkspace):
+        reads = 0
 
     r = object.__new__(HipRenderer)
-    ws = torch.zeros(64, dtype=torch.uint8)
+    ws = torch.zeros(64, dtype=torch.uint8).as_subclass(Workspace)
     t = torch.zeros(16, dtype=torch.float64)
-    r.__dict__.update(_lib=Lib(), device=torch.device("cpu"), max_bounces=3, _mesh_ws=ws, _mesh_clean={},
-                      _mesh_tables={"k": t}, _light_tables={b"l": torch.zeros(1, 6, dtype=torch.float64)},
-                      _graph_pins={}, _stream=lambda: 0)
-    table = base._MeshTable(None, None, ("k", b"l"))
-    status = [0]
-
-    def read(w):
-        reads.append(1)
-        return status[0]
-
-    monkeypatch.setattr(r, "_read_status", read, raising=False)
-    r._trace_mesh(t, 0, table, 0, 0, t, 4, t, 1, key="frame")
-    r._trace_mesh(t, 0, table, 0, 0, t, 4, t, 1, key="frame")  # clean before: no read-back
-    assert len(calls) == 2 and len(reads) == 1 and "frame" in r._mesh_clean
-    status[0] = L.ST_STACK_OVERFLOW
-    ws[4] = 1
-    with pytest.raises(RecursionError, match="more than 8 pending rays at max_bounces=3"):
-        r._trace_mesh(t, 0, table, 0, 0, t, 4, t, 1, key="other")
-    assert int(ws[4]) == 0 and "other" not in r._mesh_clean  # the sticky flag is cleared, nothing remembered
+    r.__dict__.update(_lib=Lib(), device=torch.device("cpu"), max_bounces=3, _glass_ws=ws, _lights_ws=ws, _mesh_ws=ws,
+                      _glass_clean={}, _lights_clean={}, _mesh_clean={}, _mesh_tables={"k": t},
+                      _light_tables={b"l": torch.zeros(1, 6, dtype=torch.float64)},
+                      _env_images={"d": torch.zeros(2, 4, 3, dtype=torch.float64)}, _graph_pins={}, _stream=lambda: 0)
+    glass_table, lights_table = base._GlassTable(t, b"g"), base._LightsTable(None, b"l")
+    env = base._EnvLight(types.SimpleNamespace(digest="d", texels=None), (1.0, 1.0, 1.0), 0.0)
+    table, trace = {
+        "glass": (glass_table, r._trace_glass),
+        "lights": (lights_table, r._trace_lights),
+        "env_lights": (base._EnvTable(env, lights_table, ("d", b"l")), r._trace_env),
+        "env_glass": (base._EnvTable(env, glass_table, ("d", b"g")), r._trace_env),
+        "mesh": (base._MeshTable(None, None, ("k", b"l")), r._trace_mesh),
+        "mesh_uv": (base._MeshTable(None, None, ("k", b"l"), True), r._trace_mesh),
+    }[route]
+    assert r._tracer(table) == trace
+    status = ws[:8].view(torch.int32)  # (not a counted read: the count starts below)
+    Workspace.reads = 0
+    trace(t, 0, table, 0, 0, t, 4, t, 1, key="frame")
+    trace(t, 0, table, 0, 0, t, 4, t, 1, key="frame")  # clean before: no read-back
+    assert calls == [entry, entry] and Workspace.reads == 1
+    records = {name: dict(getattr(r, name)) for name in ("_glass_clean", "_lights_clean", "_mesh_clean")}
+    assert records.pop(record) == {"frame": True} and not any(records.values())
+    status[1] = L.ST_STACK_OVERFLOW
+    with pytest.raises(RecursionError, match=f"more than {pending} pending rays at max_bounces=3"):
+        trace(t, 0, table, 0, 0, t, 4, t, 1, key="other")
+    assert calls == [entry] * 3 and Workspace.reads == 2
+    assert int(status[1]) == 0 and "other" not in getattr(r, record)  # the sticky flag is cleared, nothing remembered
 
 
 def test_the_new_methods_live_in_the_base_class():
