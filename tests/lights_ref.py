@@ -127,6 +127,58 @@ def trace(scene, table, origin, dirs, max_bounces, counts=None, level=0):
     return col
 
 
+def pushes(scene, table, origin, dirs):
+    """The reflected rays that the hits of a batch of rays send, in the order k_trace_lights pushes them
+    (the shapes at the nearest distance in scene order): a list of (indices into the batch, origins,
+    directions). ``trace``'s decisions (``specular_gain != 0`` and a light that reaches the hit) restated
+    without the colours; the bounce cap is the caller's."""
+    table = np.asarray(table, dtype=np.float64).reshape(-1, 6)
+    dx, dy, dz = (np.asarray(d, dtype=np.float64) for d in dirs)
+    ox, oy, oz = origin
+    dist = [O.intersect(sp, ox, oy, oz, dx, dy, dz) for sp in scene.spheres]
+    nearest = reduce(np.minimum, dist)
+    out = []
+    for si, (sp, d) in enumerate(zip(scene.spheres, dist)):
+        idx = np.nonzero((nearest != O.FARAWAY) & (d == nearest))[0]
+        if idx.size == 0 or sp.specular_gain == 0:
+            continue
+        sub = (lambda a: a if np.ndim(a) == 0 else a[idx])  # noqa: E731
+        hx, hy, hz, hdx, hdy, hdz, t = sub(ox), sub(oy), sub(oz), dx[idx], dy[idx], dz[idx], d[idx]
+        px, py, pz = hx + hdx * t, hy + hdy * t, hz + hdz * t
+        inv_r = 1.0 / sp.radius
+        nx, ny, nz = (px - sp.cx) * inv_r, (py - sp.cy) * inv_r, (pz - sp.cz) * inv_r
+        qx, qy, qz = px + nx * 0.0001, py + ny * 0.0001, pz + nz * 0.0001
+        reach = [np.zeros(idx.size) for _ in range(3)]
+        for row in table:
+            lx, ly, lz = O._norm(row[0] - px, row[1] - py, row[2] - pz)
+            light_d = [O.intersect(o, qx, qy, qz, lx, ly, lz) for o in scene.spheres]
+            lit = light_d[si] == reduce(np.minimum, light_d)
+            for c in range(3):
+                reach[c] = reach[c] + lit * row[3 + c]
+        need = (reach[0] != 0) | (reach[1] != 0) | (reach[2] != 0)
+        if need.any():
+            dn = O._dot(hdx, hdy, hdz, nx, ny, nz)
+            rx, ry, rz = O._norm(hdx - (nx * 2) * dn, hdy - (ny * 2) * dn, hdz - (nz * 2) * dn)
+            out.append((idx[need], (qx[need], qy[need], qz[need]), (rx[need], ry[need], rz[need])))
+    return out
+
+
+def pending_need(scene, table, origin, dirs, max_bounces, level=0):
+    """Per ray, the largest number of pending rays that k_trace_lights's depth-first walk would hold with an
+    unbounded stack (the kernel's holds 2 * max_bounces + 2; a lane that needs more drops rays and reports
+    RTX_ST_STACK_OVERFLOW): tests/mesh_ref.py's recursion over ``pushes``. An int64 array, at least 1."""
+    n = np.asarray(dirs[0]).shape[0]
+    need = np.ones(n, dtype=np.int64)
+    if level >= max_bounces or n == 0:  # the next level is black: nothing is pushed
+        return need
+    pushed = np.zeros(n, dtype=np.int64)
+    for rays, o2, d2 in pushes(scene, table, origin, dirs):
+        child = pending_need(scene, table, o2, d2, max_bounces, level + 1)
+        need[rays] = np.maximum(need[rays], pushed[rays] + child)
+        pushed[rays] += 1
+    return need
+
+
 def table_of(spec):
     """The lights table of ``spec`` as lights.lights_table builds it from the scene: every point entry
     in list order, e = intensity * colour (defaults 1 and white)."""

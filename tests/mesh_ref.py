@@ -328,6 +328,87 @@ def _shade(scene, g, table, si, mat, mesh_i, P, N, Q, V, D, max_bounces, bounded
     return out
 
 
+# ---- the kernel's stack of pending rays ----------------------------------------------------------
+def pushes(scene, g: Group, table, origin, dirs):
+    """The reflected rays that the hits of a batch of rays send, in the order k_trace_mesh pushes them: the
+    spheres at the nearest distance in scene order, then the triangle. A list of (indices into the batch,
+    origins, directions); a ray appears at most once per entry. The decisions are ``trace``'s and ``_shade``'s
+    (which shapes are at the nearest distance, ``specular_gain != 0`` and a light that reaches the hit),
+    restated without the colours; the bounce cap is the caller's."""
+    table = np.asarray(table, dtype=np.float64).reshape(-1, 6)
+    dx, dy, dz = (np.asarray(d, dtype=np.float64) for d in dirs)
+    ox, oy, oz = origin
+    n = dx.shape[0]
+    dist = [O.intersect(sp, ox, oy, oz, dx, dy, dz) for sp in scene.spheres]
+    near_s = reduce(np.minimum, dist, np.full(n, O.FARAWAY))
+    tt, num, tu, tv, _ = nearest_triangle(g, ox, oy, oz, dx, dy, dz)
+    nearest = np.minimum(near_s, tt)
+    hits = [(si, sp, (nearest != O.FARAWAY) & (d == nearest)) for si, (sp, d) in enumerate(zip(scene.spheres, dist))]
+    hits.append((-1, None, (nearest != O.FARAWAY) & (tt == nearest)))
+    out = []
+    for si, sp, hit in hits:
+        idx = np.nonzero(hit)[0]
+        if idx.size == 0:
+            continue
+        sub = (lambda a: a if np.ndim(a) == 0 else a[idx])  # noqa: E731
+        hx, hy, hz, hdx, hdy, hdz, t = sub(ox), sub(oy), sub(oz), dx[idx], dy[idx], dz[idx], nearest[idx]
+        px, py, pz = hx + hdx * t, hy + hdy * t, hz + hdz * t
+        if sp is not None:
+            inv_r = 1.0 / sp.radius
+            nx, ny, nz = (px - sp.cx) * inv_r, (py - sp.cy) * inv_r, (pz - sp.cz) * inv_r
+            gx, gy, gz = nx, ny, nz
+            gains = np.full(idx.size, sp.specular_gain)
+        else:
+            r = num[idx]
+            flip = np.where(O._dot(g.ng[r, 0], g.ng[r, 1], g.ng[r, 2], hdx, hdy, hdz) > 0, -1.0, 1.0)
+            gx, gy, gz = g.ng[r, 0] * flip, g.ng[r, 1] * flip, g.ng[r, 2] * flip
+            u, v = tu[idx], tv[idx]
+            w0 = (1.0 - u) - v
+            sx, sy, sz = ((w0 * g.n0[r, c] + u * g.n1[r, c]) + v * g.n2[r, c] for c in range(3))
+            sx, sy, sz = O._norm(sx, sy, sz)
+            back = np.where(O._dot(sx, sy, sz, gx, gy, gz) < 0, -1.0, 1.0)
+            nx, ny, nz = (np.where(g.smooth[r], s * back, f) for s, f in ((sx, gx), (sy, gy), (sz, gz)))
+            gains = np.array([m.specular_gain for m in g.mats], dtype=np.float64)[g.mesh[r]]
+        qx, qy, qz = px + gx * 0.0001, py + gy * 0.0001, pz + gz * 0.0001
+        reach = [np.zeros(idx.size) for _ in range(3)]
+        for row in table:
+            lx, ly, lz = O._norm(row[0] - px, row[1] - py, row[2] - pz)
+            light_d = [O.intersect(o, qx, qy, qz, lx, ly, lz) for o in scene.spheres]
+            tself = light_d[si] if si >= 0 else np.full(idx.size, O.FARAWAY)
+            tri_d, _ = _min_by_mesh(g, qx, qy, qz, lx, ly, lz)
+            lit = tself == np.minimum(reduce(np.minimum, light_d, np.full(idx.size, O.FARAWAY)), tri_d)
+            for c in range(3):
+                reach[c] = reach[c] + lit * row[3 + c]
+        need = (gains != 0) & ((reach[0] != 0) | (reach[1] != 0) | (reach[2] != 0))
+        if need.any():
+            dn = O._dot(hdx, hdy, hdz, nx, ny, nz)
+            rx, ry, rz = O._norm(hdx - (nx * 2) * dn, hdy - (ny * 2) * dn, hdz - (nz * 2) * dn)
+            out.append((idx[need], (qx[need], qy[need], qz[need]), (rx[need], ry[need], rz[need])))
+    return out
+
+
+def pending_need(scene, g: Group, table, origin, dirs, max_bounces, level=0):
+    """Per ray, the largest number of pending rays that k_trace_mesh's depth-first walk would hold with an
+    unbounded stack (the kernel's holds 2 * max_bounces + 2; a lane that needs more drops rays and reports
+    RTX_ST_STACK_OVERFLOW). Arguments as ``trace``; an int64 array, at least 1: the ray itself.
+
+    The walk pops a ray, shades its hits one per round (``pushes``' order) and, when level < max_bounces,
+    each hit pushes at most one ray; it pops the last pushed first and finishes that ray's whole tree before
+    the next. So the j-th ray a node pushed (from 0) is popped with j siblings still below it, and a node
+    needs max(1, max_j (j + need of its j-th child)) entries, itself included (tests/glass_ref.py's
+    recursion). With k + 1 shapes at the nearest distance on every level that is max_bounces * k + 1."""
+    n = np.asarray(dirs[0]).shape[0]
+    need = np.ones(n, dtype=np.int64)
+    if level >= max_bounces or n == 0:  # the next level is black: nothing is pushed
+        return need
+    pushed = np.zeros(n, dtype=np.int64)
+    for rays, o2, d2 in pushes(scene, g, table, origin, dirs):
+        child = pending_need(scene, g, table, o2, d2, max_bounces, level + 1)
+        need[rays] = np.maximum(need[rays], pushed[rays] + child)
+        pushed[rays] += 1
+    return need
+
+
 def table_of(spec):
     """The lights table of ``spec`` as the renderer builds it: every point light (lights.lights_table)
     if one of them has an intensity or a colour, else the one row (lights[0], 1, 1, 1)."""

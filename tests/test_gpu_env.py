@@ -7,7 +7,8 @@ The lookup is bilinear, so the few ulp between the device's atan2 / asin and Num
 about as much (images of 64 x 32 or smaller; the drift grows with the image's width). Each frame case
 also has to differ from the same render without the EnvironmentLight on at least half the pinned
 count of changed pixels: a renderer that ignores the light fails every case. Nothing here provokes an
-overflow of a lane's stack.
+overflow of a lane's stack: the walk is the lights kernel's (one text, rtx_lights_walk.inc), whose stack
+tests/test_gpu_lights_limits.py fills to its last entry and one over.
 """
 
 import copy

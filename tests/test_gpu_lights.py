@@ -6,7 +6,8 @@ association), and its uint8 frame must be identical, no pixel excluded: tests/te
 that no pixel of a case sits within 1e-9 of a quantisation step. Which rays exist, what they hit and which
 light reaches a hit are decisions the kernel must take bit for bit like the restatement; a wrong one moves a
 pixel by far more than the bar. The counts asserted with each case keep it from passing on a frame that
-proves nothing. Nothing here provokes an overflow of a lane's stack: that path is covered on the host.
+proves nothing. Nothing here provokes an overflow of a lane's stack: the stack filled to its last entry and one
+over, and a worker's second item at a cap above 0, are in tests/test_gpu_lights_limits.py.
 """
 
 import copy

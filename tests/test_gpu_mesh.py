@@ -6,8 +6,9 @@ frame must be identical, no pixel excluded: tests/test_mesh_cpu.py checks that n
 within 1e-9 of a quantisation step, that each frame exercises what it is meant to, and that the tree's
 pruning changes no frame of the restatement. Which rays exist, which triangle they hit and which light
 reaches a hit are decisions the kernel must take bit for bit like the restatement; a wrong one moves a
-pixel by far more than the bar. Nothing here provokes an overflow of a lane's stack: that path is covered
-on the host.
+pixel by far more than the bar. Nothing here provokes an overflow of a lane's stack: the stack filled to
+its last entry and one over, a worker's second item and the far, deep and grazing cases are in
+tests/test_gpu_mesh_limits.py.
 """
 
 import copy

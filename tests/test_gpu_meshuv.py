@@ -7,7 +7,8 @@ bar for float64 colour, |GPU - restatement| <= 1e-12 * max(1, |colour|), and its
 identical, no pixel excluded: tests/test_meshuv_cpu.py checks that no pixel of a case sits within 1e-9 of a
 quantisation step, that each frame exercises what it is meant to (wrapped and negative coordinates, the
 torus's seam segment, reflected hits on textured triangles), and that the tree's pruning changes no frame of
-the restatement. Nothing here provokes an overflow of a lane's stack: that path is covered on the host.
+the restatement. Nothing here provokes an overflow of a lane's stack: the stack filled to its last entry and one
+over, and a worker's second item, through this kernel too, are in tests/test_gpu_mesh_limits.py.
 """
 
 import copy
