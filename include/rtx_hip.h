@@ -43,6 +43,7 @@
  *   rtx_env_sample, rtx_trace_lights_env, rtx_trace_glass_env
  *                       <- no counterpart (raytrace_scene adds nothing on a miss, base.py:100-121): an
  *                          equirectangular environment map that every ray which meets no shape samples
+ *   rtx_mesh_build      <- no counterpart: the table of rtx_trace_mesh (rows, tree, boxes) made on the device
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -76,7 +77,8 @@ extern "C" {
 /* (rtx_primary_aovs*, rtx_edge_mask, rtx_sample_dirs and rtx_resolve_scatter were added to version 3:
  * new symbols only, nothing that existed changed; so were rtx_camera_rays, rtx_occlusion,
  * rtx_trace_glass with rtx_glass_workspace_bytes, and rtx_trace_lights with rtx_lights_workspace_bytes,
- * and rtx_env_sample, rtx_trace_lights_env and rtx_trace_glass_env) */
+ * and rtx_env_sample, rtx_trace_lights_env and rtx_trace_glass_env, rtx_trace_mesh and rtx_trace_mesh_uv with
+ * rtx_mesh_workspace_bytes, and rtx_mesh_build with rtx_mesh_build_nodes and rtx_mesh_build_workspace_bytes) */
 
 /* ---- scene blob layout (float64 words) ---- */
 enum {
@@ -843,6 +845,49 @@ int rtx_trace_mesh_uv(const double* scene, int n_spheres, const double* mesh, in
                       const double* lights, int n_lights, const double* origins, int64_t origin_stride,
                       const double* dirs, int64_t n, int max_bounces, void* out, int out_kind, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* The mesh table made on the device (HipRenderer.mesh_build = "device"): rtx_mesh_build fills
+ * a skeleton of the table of rtx_trace_mesh / rtx_trace_mesh_uv from the meshes' raw arrays. The contract is
+ * the host's table: after the call `table` holds, word for word, the float64 values of
+ * python_ray_tracer_amd.meshes.mesh_table for the same meshes and max_leaf (only the sign of a zero is
+ * free), so the tree, its margins and every frame rendered from it are the host-built table's.
+ * Inputs, all on the device: `vertices` double [n_vertices][3], the meshes' vertices one after the other;
+ * `faces` int32 [n_triangles][3], indices into `vertices` (each mesh's already offset by its vertex base),
+ * the triangles in group order; `tri_mesh` int32 [n_triangles], each triangle's mesh; `normals` double
+ * [n_vertices][3] and `mesh_smooth` int32 [n_meshes] (1: the mesh has vertex normals), both null when no
+ * mesh is smooth; `uvs` double [n_triangles][RTX_UV_WORDS] per corner, or null (zeros).
+ * `table`, double [table_words] on the device, is the skeleton (meshes.device_inputs): the header, the
+ * material rows, every node's first, count and skip (they depend on n_triangles and max_leaf alone) and the
+ * texel blocks; `header` is a HOST copy of its first RTX_MESH_HDR_WORDS words, read at the call. The call
+ * writes the triangle rows in leaf order, the nodes' boxes and margins and, where the header names a UV
+ * part, that part. The arithmetic is meshes.triangle_rows' and mesh_table_entry's, float64 without
+ * contraction: e1 = v1 - v0, e2 = v2 - v0, N_g = cross(e1, e2) / sqrt((x*x + y*y) + z*z); a triangle's box
+ * is min / max of v0, v0 + e1, v0 + e2, its centre (lo + hi) * 0.5; a level sorts every segment longer than
+ * max_leaf by its centres along the first largest extent, ties by the triangle's number (-0.0 equals 0.0),
+ * and cuts it at s + (len + 1) / 2; a node's margin is 2e-7 * (1 + ((mx*mx + my*my) + mz*mz)), m the larger
+ * of |lo| and |hi| per axis. The sorts are rocPRIM's stable device radix sort over the workspace.
+ * max_leaf: the most triangles of a leaf, 0 for one leaf. rtx_mesh_build_nodes(n_triangles, max_leaf) is
+ * that tree's node count (0 for arguments out of range); rtx_mesh_build_workspace_bytes(n_triangles, n_nodes)
+ * the workspace (0 for n_triangles outside 1..RTX_MAX_TRIANGLES or n_nodes outside 1..2 n_triangles). The
+ * workspace needs no initialisation. Its first two uint32 words are the build's status, written by the
+ * call: word 0 the lowest number of a triangle whose normal cannot be normalised (RTX_MB_NONE: none; the
+ * table is then not to be used), word 1 non-zero if a face index or mesh number was out of range (it was
+ * read as 0; nothing is read or written out of bounds).
+ * Asynchronous on `stream`, never allocates, never synchronises. RTX_E_ARG (before any HIP call) for a null
+ * vertices, faces, tri_mesh, header, table or workspace, normals without mesh_smooth or the reverse,
+ * n_triangles outside 1..RTX_MAX_TRIANGLES, n_vertices outside 1..2^31 - 1, a negative max_leaf, a header
+ * that is not a mesh table's of n_triangles triangles and rtx_mesh_build_nodes nodes or whose parts do not
+ * fit it, table_words below the header's word count (a skeleton shorter than its own header says) or above
+ * 2^31 - 1, and a workspace smaller than rtx_mesh_build_workspace_bytes; RTX_E_WORKSPACE if rocPRIM asks
+ * for more temporary storage than the workspace sets aside. The call is not part of rtx_last_launches'
+ * record, which describes k_render_fast launches only. */
+#define RTX_MB_NONE 0xFFFFFFFFu
+int64_t rtx_mesh_build_nodes(int64_t n_triangles, int max_leaf);
+size_t rtx_mesh_build_workspace_bytes(int64_t n_triangles, int64_t n_nodes);
+int rtx_mesh_build(const double* vertices, int64_t n_vertices, const int32_t* faces, const int32_t* tri_mesh,
+                   int64_t n_triangles, const double* normals, const int32_t* mesh_smooth, const double* uvs,
+                   const double* header, double* table, int64_t table_words, int max_leaf, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

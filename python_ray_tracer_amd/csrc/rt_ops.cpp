@@ -23,6 +23,8 @@
 //                        every point light of a table (rtx_trace_lights); allocates its workspace
 //   rt::trace_mesh    <- no counterpart (the reference's only Shape is the sphere): raytrace_scene on explicit rays
 //                        through the spheres and the triangles of a mesh table (rtx_trace_mesh)
+//   rt::mesh_build    <- no counterpart: the table of rt::trace_mesh made on the device from the meshes' arrays
+//                        (rtx_mesh_build), value for value the host's meshes.mesh_table
 //   rt::trace_mesh_uv <- no counterpart: rt::trace_mesh on a table with texture coordinates and texel blocks
 //                        (rtx_trace_mesh_uv): image textures on meshes
 //   rt::env_sample, rt::trace_lights_env, rt::trace_glass_env
@@ -1249,6 +1251,102 @@ std::tuple<std::optional<at::Tensor>, at::Tensor> camera_rays_meta(const at::Ten
   return {origins, at::empty({3, n}, opts)};
 }
 
+// ---- rt::mesh_build: the mesh table made on the device (rtx_mesh_build) -------------------------------------
+// Shapes and ranges of its arguments, shared by the kernel and its Meta form: returns T.
+int64_t check_mesh_build(const at::Tensor& vertices, const at::Tensor& faces, const at::Tensor& tri_mesh,
+                         const std::optional<at::Tensor>& normals, const std::optional<at::Tensor>& mesh_smooth,
+                         const std::optional<at::Tensor>& uvs, const at::Tensor& skeleton, int64_t max_leaf,
+                         const at::Tensor& workspace) {
+  TORCH_CHECK(vertices.scalar_type() == at::kDouble && vertices.dim() == 2 && vertices.size(1) == 3 &&
+                  vertices.size(0) >= 1 && vertices.size(0) <= INT32_MAX,
+              "vertices must be ", at::kDouble, " [V, 3] with V >= 1, got ", vertices.scalar_type(), " ", vertices.sizes());
+  TORCH_CHECK(faces.scalar_type() == at::kInt && faces.dim() == 2 && faces.size(1) == 3 && faces.size(0) >= 1 &&
+                  faces.size(0) <= RTX_MAX_TRIANGLES,
+              "faces must be ", at::kInt, " [T, 3] with T in 1..", (int)RTX_MAX_TRIANGLES, ", got ", faces.scalar_type(),
+              " ", faces.sizes());
+  const int64_t T = faces.size(0);
+  TORCH_CHECK(tri_mesh.scalar_type() == at::kInt && tri_mesh.dim() == 1 && tri_mesh.size(0) == T, "tri_mesh must be ",
+              at::kInt, " [T] with T = ", T, ", got ", tri_mesh.scalar_type(), " ", tri_mesh.sizes());
+  TORCH_CHECK(normals.has_value() == mesh_smooth.has_value(), "normals and mesh_smooth are given together or not at all");
+  if (normals.has_value()) {
+    TORCH_CHECK(normals->scalar_type() == at::kDouble && normals->sizes() == vertices.sizes(), "normals must be ",
+                at::kDouble, " [V, 3] like the vertices, got ", normals->scalar_type(), " ", normals->sizes());
+    TORCH_CHECK(mesh_smooth->scalar_type() == at::kInt && mesh_smooth->dim() == 1 && mesh_smooth->size(0) >= 1,
+                "mesh_smooth must be ", at::kInt, " [M], got ", mesh_smooth->scalar_type(), " ", mesh_smooth->sizes());
+  }
+  if (uvs.has_value())
+    TORCH_CHECK(uvs->scalar_type() == at::kDouble && uvs->dim() == 2 && uvs->size(0) == T && uvs->size(1) == RTX_UV_WORDS,
+                "uvs must be ", at::kDouble, " [T, ", (int)RTX_UV_WORDS, "], got ", uvs->scalar_type(), " ", uvs->sizes());
+  TORCH_CHECK(skeleton.scalar_type() == at::kDouble && skeleton.dim() == 1 && skeleton.numel() >= RTX_MESH_HDR_WORDS &&
+                  skeleton.numel() <= INT32_MAX,
+              "skeleton must be ", at::kDouble, " [words] with at least ", (int)RTX_MESH_HDR_WORDS,
+              " words (meshes.device_inputs), got ", skeleton.scalar_type(), " ", skeleton.sizes());
+  TORCH_CHECK(max_leaf >= 0 && max_leaf <= INT32_MAX, "max_leaf must be positive, or 0 for one leaf, got ", max_leaf);
+  TORCH_CHECK(workspace.scalar_type() == at::kByte && workspace.dim() == 1, "workspace must be ", at::kByte,
+              " [bytes], got ", workspace.scalar_type(), " ", workspace.sizes());
+  return T;
+}
+
+// Fills `skeleton` in place; returns the build's two status words, int32 [2] (a copy: the workspace is the caller's
+// to reuse). check: the skeleton's header against its length and the workspace's size are refused here, and a
+// degenerate triangle raises (a synchronisation); without it the library's own codes and the status speak.
+at::Tensor mesh_build(const at::Tensor& vertices, const at::Tensor& faces, const at::Tensor& tri_mesh,
+                      const std::optional<at::Tensor>& normals, const std::optional<at::Tensor>& mesh_smooth,
+                      const std::optional<at::Tensor>& uvs, at::Tensor& skeleton, int64_t max_leaf, at::Tensor& workspace,
+                      bool check) {
+  check_gpu(skeleton, "skeleton", at::kDouble);
+  const at::OptionalDeviceGuard guard(at::device_of(skeleton));
+  const auto on = [&](const at::Tensor& t, const char* name, at::ScalarType dtype) {
+    check_gpu(t, name, dtype);
+    check_same_device(skeleton, t, name);
+  };
+  on(vertices, "vertices", at::kDouble), on(faces, "faces", at::kInt), on(tri_mesh, "tri_mesh", at::kInt);
+  on(workspace, "workspace", at::kByte);
+  if (normals.has_value()) on(*normals, "normals", at::kDouble);
+  if (mesh_smooth.has_value()) on(*mesh_smooth, "mesh_smooth", at::kInt);
+  if (uvs.has_value()) on(*uvs, "uvs", at::kDouble);
+  const int64_t T = check_mesh_build(vertices, faces, tri_mesh, normals, mesh_smooth, uvs, skeleton, max_leaf, workspace);
+  // (one synchronous copy of the header: the entry reads it on the host)
+  const at::Tensor head = skeleton.narrow(0, 0, RTX_MESH_HDR_WORDS).to(at::kCPU).contiguous();
+  const double* h = head.data_ptr<double>();
+  if (check) {
+    TORCH_CHECK(h[RTX_MH_MAGIC] == RTX_MESH_MAGIC && h[RTX_MH_NTRI] == (double)T,
+                "skeleton is not a mesh table of ", T, " triangles (meshes.device_inputs)");
+    TORCH_CHECK(h[RTX_MH_WORDS] <= (double)skeleton.numel(), "skeleton has ", skeleton.numel(),
+                " words, fewer than its header says (", h[RTX_MH_WORDS], ")");
+    const size_t need = rtx_mesh_build_workspace_bytes(T, rtx_mesh_build_nodes(T, (int)max_leaf));
+    TORCH_CHECK((size_t)workspace.numel() >= need, "workspace too small: ", workspace.numel(), " < ", need,
+                " bytes (rtx_mesh_build_workspace_bytes)");
+    if (mesh_smooth.has_value())
+      TORCH_CHECK((double)mesh_smooth->size(0) == h[RTX_MH_NMESH], "mesh_smooth must have one flag per mesh (",
+                  h[RTX_MH_NMESH], "), got ", mesh_smooth->sizes());
+  }
+  check_rc(rtx_mesh_build(vertices.data_ptr<double>(), vertices.size(0), faces.data_ptr<int32_t>(),
+                          tri_mesh.data_ptr<int32_t>(), T, normals.has_value() ? normals->data_ptr<double>() : nullptr,
+                          mesh_smooth.has_value() ? mesh_smooth->data_ptr<int32_t>() : nullptr,
+                          uvs.has_value() ? uvs->data_ptr<double>() : nullptr, h, skeleton.data_ptr<double>(),
+                          skeleton.numel(), (int)max_leaf, workspace.data_ptr(), (size_t)workspace.numel(),
+                          stream_of(skeleton)),
+           "rtx_mesh_build");
+  at::Tensor status = workspace.narrow(0, 0, 8).view(at::kInt).clone();
+  if (check) {
+    const at::Tensor st = status.to(at::kCPU);
+    const int32_t* w = st.data_ptr<int32_t>();
+    TORCH_CHECK(w[1] == 0, "rtx_mesh_build: a face index or a mesh number is out of range");
+    TORCH_CHECK((uint32_t)w[0] == RTX_MB_NONE, "rtx_mesh_build: triangle ", (uint32_t)w[0],
+                " is degenerate (its normal cannot be normalised)");
+  }
+  return status;
+}
+
+at::Tensor mesh_build_meta(const at::Tensor& vertices, const at::Tensor& faces, const at::Tensor& tri_mesh,
+                           const std::optional<at::Tensor>& normals, const std::optional<at::Tensor>& mesh_smooth,
+                           const std::optional<at::Tensor>& uvs, at::Tensor& skeleton, int64_t max_leaf,
+                           at::Tensor& workspace, bool) {
+  check_mesh_build(vertices, faces, tri_mesh, normals, mesh_smooth, uvs, skeleton, max_leaf, workspace);
+  return at::empty({2}, skeleton.options().dtype(at::kInt));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rt, m) {
@@ -1282,6 +1380,8 @@ TORCH_LIBRARY(rt, m) {
         "int max_bounces, int out_kind, bool check=True) -> Tensor");
   m.def("trace_mesh_uv(Tensor scene, int n_spheres, Tensor mesh, Tensor lights, Tensor origins, Tensor dirs, "
         "int max_bounces, int out_kind, bool check=True) -> Tensor");
+  m.def("mesh_build(Tensor vertices, Tensor faces, Tensor tri_mesh, Tensor? normals, Tensor? mesh_smooth, Tensor? uvs, "
+        "Tensor(a!) skeleton, int max_leaf, Tensor(b!) workspace, bool check=True) -> Tensor");
   m.def("env_sample(Tensor texels, float[] gain, float turn, Tensor dirs) -> Tensor");
   m.def("trace_lights_env(Tensor scene, int n_spheres, Tensor lights, Tensor origins, Tensor dirs, int max_bounces, "
         "int out_kind, Tensor texels, float[] gain, float turn, bool check=True) -> Tensor");
@@ -1324,6 +1424,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("trace_lights", &trace_lights);
   m.impl("trace_mesh", &trace_mesh);
   m.impl("trace_mesh_uv", &trace_mesh_uv);
+  m.impl("mesh_build", &mesh_build);
   m.impl("env_sample", &env_sample);
   m.impl("trace_lights_env", &trace_lights_env);
   m.impl("trace_glass_env", &trace_glass_env);
@@ -1352,6 +1453,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("trace_lights", &trace_lights);
   m.impl("trace_mesh", &trace_mesh);
   m.impl("trace_mesh_uv", &trace_mesh_uv);
+  m.impl("mesh_build", &mesh_build);
   m.impl("env_sample", &env_sample);
   m.impl("trace_lights_env", &trace_lights_env);
   m.impl("trace_glass_env", &trace_glass_env);
@@ -1378,6 +1480,7 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("trace_lights", &trace_lights_meta);
   m.impl("trace_mesh", &trace_mesh_meta);
   m.impl("trace_mesh_uv", &trace_mesh_meta);
+  m.impl("mesh_build", &mesh_build_meta);
   m.impl("env_sample", &env_sample_meta);
   m.impl("trace_lights_env", &trace_lights_env_meta);
   m.impl("trace_glass_env", &trace_glass_env_meta);

@@ -37,6 +37,7 @@ MAX_POINT_LIGHTS = 8  # the rows of a multi-light scene's table (rtx_trace_light
 LIGHTS_MAX_BOUNCES = 16  # the largest bounce cap of a multi-light scene (rtx_trace_lights)
 MAX_TRIANGLES = 1 << 20  # the triangles of a mesh scene (rtx_trace_mesh)
 MESH_MAX_BOUNCES = 16  # the largest bounce cap of a mesh scene (rtx_trace_mesh)
+MB_NONE = 0xFFFFFFFF  # rtx_mesh_build's status word 0 when no triangle is degenerate
 ENV_MAX_TEXELS = 1 << 23  # the largest environment image (rtx_env_t)
 MAGIC = 5527384.0
 UNBOUNDED = -1
@@ -130,6 +131,9 @@ EXPORTS = (
     "rtx_mesh_workspace_bytes",
     "rtx_trace_mesh",
     "rtx_trace_mesh_uv",
+    "rtx_mesh_build_nodes",
+    "rtx_mesh_build_workspace_bytes",
+    "rtx_mesh_build",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -234,6 +238,10 @@ _SIGS = {
                               _c_void_p, _i32, _c_void_p, _size, _c_void_p]),
     "rtx_trace_mesh_uv": (_i32, [_c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64,
                                  _i32, _c_void_p, _i32, _c_void_p, _size, _c_void_p]),
+    "rtx_mesh_build_nodes": (_i64, [_i64, _i32]),
+    "rtx_mesh_build_workspace_bytes": (_size, [_i64, _i64]),
+    "rtx_mesh_build": (_i32, [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                              _c_void_p, _i64, _i32, _c_void_p, _size, _c_void_p]),
 }
 
 _lib = None

@@ -10,6 +10,7 @@ ValueError before any device call.
 from __future__ import annotations
 
 import hashlib
+from typing import NamedTuple
 
 import numpy as np
 
@@ -529,21 +530,7 @@ def mesh_table_entry(shapes, max_leaf=4) -> tuple:
         parts.append(uvs[order].ravel())
         words += uvs.size
         head[MH_TEXELS] = words
-        blocks = {}
-        for i, mesh in enumerate(sh for sh in shapes if isinstance(sh, TriangleMesh)):
-            tex = mesh.shader.diffuse_color
-            if not _is_image(tex):
-                continue
-            t = _mesh_image(mesh, i)
-            digest = getattr(tex, "digest", None) or _texels_digest(t)
-            if digest not in blocks:
-                blocks[digest] = words
-                parts.append(t.ravel())
-                words += t.size
-            mats[i, L.M_TR] = blocks[digest]
-        if words >= 1 << 31:
-            raise ValueError(f"the mesh table would have {words} words; rtx_trace_mesh_uv takes fewer than 2^31")
-        head[MH_WORDS] = words
+        head[MH_WORDS] = _texel_blocks(shapes, mats, words, parts)
     parts[2] = mats.ravel()
     table = np.concatenate(parts)
     table.setflags(write=False)
@@ -554,6 +541,168 @@ def mesh_table_entry(shapes, max_leaf=4) -> tuple:
 
 
 _TABLES: dict = {}  # (content digest, max_leaf) -> table
+
+
+def _texel_blocks(shapes, mats, words: int, parts: list) -> int:
+    """One texel block per distinct image of ``shapes``' meshes appended to ``parts`` from word ``words`` on, each
+    image mesh's material row (``mats``) given its block's offset: the table's length with them. ValueError for
+    a table of 2^31 words or more."""
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+
+    blocks = {}
+    for i, mesh in enumerate(sh for sh in shapes if isinstance(sh, TriangleMesh)):
+        tex = mesh.shader.diffuse_color
+        if not _is_image(tex):
+            continue
+        t = _mesh_image(mesh, i)
+        digest = getattr(tex, "digest", None) or _texels_digest(t)
+        if digest not in blocks:
+            blocks[digest] = words
+            parts.append(t.ravel())
+            words += t.size
+        mats[i, L.M_TR] = blocks[digest]
+    if words >= 1 << 31:
+        raise ValueError(f"the mesh table would have {words} words; rtx_trace_mesh_uv takes fewer than 2^31")
+    return words
+
+
+# ---------------------------------------------------------------------------------------------
+# the device build (rtx_mesh_build, DESIGN.md §19)
+# ---------------------------------------------------------------------------------------------
+class DeviceInputs(NamedTuple):
+    """What rtx_mesh_build makes a scene's table from: the meshes' arrays one after the other and the
+    skeleton, the table with everything that does not depend on a vertex."""
+
+    vertices: np.ndarray  # float64 [V, 3]
+    faces: np.ndarray  # int32 [T, 3], into ``vertices``
+    tri_mesh: np.ndarray  # int32 [T]: each triangle's mesh
+    normals: np.ndarray | None  # float64 [V, 3] (zeros for a flat mesh), None if no mesh is smooth
+    smooth: np.ndarray | None  # int32 [M]: 1 for a mesh with vertex normals; None with ``normals``
+    uvs: np.ndarray | None  # float64 [T, UV_WORDS] (zeros for a mesh without), None for a table without a UV part
+    skeleton: np.ndarray  # float64 [words]
+    first_triangle: np.ndarray  # int64 [M]: each mesh's first triangle number
+    max_leaf: int  # rtx_mesh_build's: 0 for one leaf
+
+
+def tree_ranges(T: int, max_leaf):
+    """(starts, ends [N]) of the nodes of ``build_tree`` over ``T`` boxes in depth-first order: they depend on
+    ``T`` and ``max_leaf`` alone. Cached."""
+    hit = _RANGES.get((T, max_leaf))
+    if hit is not None:
+        return hit
+    leaf = T if max_leaf is None else int(max_leaf)
+    starts, ends = [np.array([0])], [np.array([T])]
+    s, e = starts[0], ends[0]
+    while True:
+        big = (e - s) > leaf
+        s, e = s[big], e[big]
+        if s.size == 0:
+            break
+        mid = s + (e - s + 1) // 2
+        s, e = np.concatenate([s, mid]), np.concatenate([mid, e])
+        starts.append(s)
+        ends.append(e)
+    s, e = np.concatenate(starts), np.concatenate(ends)
+    dfs = np.lexsort((-(e - s), s))
+    if len(_RANGES) >= 8:
+        _RANGES.pop(next(iter(_RANGES)))
+    _RANGES[(T, max_leaf)] = s[dfs], e[dfs]
+    return _RANGES[(T, max_leaf)]
+
+
+def device_inputs(shapes, max_leaf=4) -> DeviceInputs:
+    """The inputs of rtx_mesh_build for the meshes of ``shapes``, validated; cached by content like
+    ``mesh_table``. The skeleton is ``mesh_table``'s header, material rows, every node's first, count and skip
+    and the texel blocks, with zeros where the build writes (the rows, the nodes' boxes and margins, the UV
+    part). ValueError as ``mesh_table``, but for a degenerate face: the device finds those."""
+    return device_inputs_entry(shapes, max_leaf)[0]
+
+
+def device_inputs_entry(shapes, max_leaf=4) -> tuple:
+    """(``device_inputs``, its content key): the key is ``mesh_table_entry``'s."""
+    from python_ray_tracer_amd.infrastructure.hip import _lib as L
+
+    if max_leaf is not None and (isinstance(max_leaf, bool) or int(max_leaf) != max_leaf or max_leaf < 1):
+        raise ValueError(f"max_leaf must be None or an int >= 1, got {max_leaf!r}")
+    shapes = list(shapes)
+    key = (_content_digest(shapes), max_leaf)
+    hit = _INPUTS.get(key)
+    if hit is not None:
+        return hit, key
+    meshes = [sh for sh in shapes if isinstance(sh, TriangleMesh)]
+    if not meshes:
+        raise ValueError("no TriangleMesh among the shapes")
+    verts, faces, tri_mesh, normals, smooth, uvs, mats, first, base, vbase = [], [], [], [], [], [], [], [], 0, 0
+    for i, mesh in enumerate(meshes):
+        v, f, n = _mesh_arrays(mesh, i)
+        F = f.shape[0]
+        uv = _mesh_uvs(mesh, i, F)
+        mats.append(_mesh_material(mesh, i))
+        if base + F > MAX_TRIANGLES:
+            raise ValueError(f"at most {MAX_TRIANGLES} triangles per scene (RTX_MAX_TRIANGLES), got more")
+        verts.append(v)
+        faces.append(f + vbase)
+        tri_mesh.append(np.full(F, i, dtype=np.int32))
+        normals.append(np.zeros_like(v) if n is None else n)
+        smooth.append(0 if n is None else 1)
+        uvs.append(np.zeros((F, UV_WORDS)) if uv is None else uv.reshape(F, UV_WORDS))
+        first.append(base)
+        base += F
+        vbase += v.shape[0]
+    if vbase >= 1 << 31:
+        raise ValueError(f"the meshes have {vbase} vertices; rtx_mesh_build takes fewer than 2^31")
+    mats = np.asarray(mats, dtype=np.float64).reshape(len(mats), -1)
+    T = base
+    s, e = tree_ranges(T, max_leaf)
+    N = s.shape[0]
+    nodes = np.zeros((N, L.NODE_WORDS))
+    inner = np.zeros(N, dtype=bool)
+    inner[:-1] = s[1:] == s[:-1]
+    nodes[:, L.N_FIRST] = s
+    nodes[:, L.N_COUNT] = np.where(inner, 0, e - s)
+    nodes[:, L.N_SKIP] = np.searchsorted(s, e, side="left")
+    head = np.zeros(HDR_WORDS)
+    tris_at = HDR_WORDS
+    mats_at = tris_at + T * TRI_WORDS
+    nodes_at = mats_at + mats.size
+    words = nodes_at + nodes.size
+    head[[MH_MAGIC, MH_NTRI, MH_NMESH, MH_NNODES, MH_TRIS, MH_MATS, MH_NODES, MH_WORDS]] = (
+        MAGIC, T, mats.shape[0], N, tris_at, mats_at, nodes_at, words)
+    parts = [head, np.zeros(T * TRI_WORDS), mats, nodes.ravel()]
+    image = has_image(shapes)
+    if image:
+        head[MH_UVS] = words
+        parts.append(np.zeros(T * UV_WORDS))
+        words += T * UV_WORDS
+        head[MH_TEXELS] = words
+        head[MH_WORDS] = _texel_blocks(shapes, mats, words, parts)
+    parts[2] = mats.ravel()
+    skeleton = np.concatenate(parts)
+    any_smooth = any(smooth)
+    out = DeviceInputs(np.ascontiguousarray(np.concatenate(verts)),
+                       np.ascontiguousarray(np.concatenate(faces), dtype=np.int32), np.concatenate(tri_mesh),
+                       np.ascontiguousarray(np.concatenate(normals)) if any_smooth else None,
+                       np.asarray(smooth, dtype=np.int32) if any_smooth else None,
+                       np.ascontiguousarray(np.concatenate(uvs)) if image else None, skeleton,
+                       np.asarray(first, dtype=np.int64), 0 if max_leaf is None else int(max_leaf))
+    for a in out[:7]:
+        if a is not None:
+            a.setflags(write=False)
+    if len(_INPUTS) >= 8:
+        _INPUTS.pop(next(iter(_INPUTS)))
+    _INPUTS[key] = out
+    return out, key
+
+
+_INPUTS: dict = {}  # (content digest, max_leaf) -> DeviceInputs
+_RANGES: dict = {}  # (T, max_leaf) -> (starts, ends) of the tree's nodes
+
+
+def degenerate_face_error(inputs: DeviceInputs, triangle: int) -> ValueError:
+    """``triangle_rows``' error for the group's triangle ``triangle`` (rtx_mesh_build's status word)."""
+    i = int(np.searchsorted(inputs.first_triangle, triangle, side="right")) - 1
+    return ValueError(f"mesh {i}: face {int(triangle - inputs.first_triangle[i])} is degenerate (its normal cannot be "
+                      "normalised)")
 
 
 def check_table(table) -> None:

@@ -77,6 +77,16 @@ that device's current HIP stream and returns a new tensor):
   ``rt::trace_mesh`` on a table with texture coordinates and texel blocks (rtx_trace_mesh_uv; DESIGN.md §18):
   the table ``meshes.mesh_table`` builds when a mesh has an ``ImageTexture``. With ``check=True`` the offsets
   of the two new parts are checked against the table's length as well.
+* ``rt::mesh_build(vertices, faces, tri_mesh, normals, mesh_smooth, uvs, skeleton, max_leaf, workspace,
+  check=True)`` — the table of ``rt::trace_mesh`` / ``rt::trace_mesh_uv`` made on the device (rtx_mesh_build;
+  contract in include/rtx_hip.h): the device arrays of ``meshes.device_inputs`` (float64 [V, 3],
+  int32 [T, 3], int32 [T], float64 [V, 3] and int32 [M] or None, float64 [T, 6] or None), ``skeleton`` its
+  float64 [words] skeleton, filled in place to the values of ``meshes.mesh_table``, ``max_leaf`` the leaf size
+  (0: one leaf), ``workspace`` uint8 of at least ``rtx_mesh_build_workspace_bytes``. Returns the build's status
+  words, int32 [2]: the lowest degenerate triangle (-1: none) and whether an index was out of range. The
+  skeleton's header is read back (one small synchronous copy); with ``check=True`` a skeleton shorter than its
+  header says and a workspace that is too small raise here, and so does a degenerate triangle (a
+  synchronisation); with ``check=False`` the library's own error codes and the status words speak.
 * ``rt::env_sample(texels, gain, turn, dirs)``, ``rt::trace_lights_env(scene, n_spheres, lights, origins, dirs,
   max_bounces, out_kind, texels, gain, turn, check=True)`` and ``rt::trace_glass_env(scene, n_spheres, glass,
   origins, dirs, max_bounces, out_kind, texels, gain, turn, check=True)`` — the environment map (rtx_env_sample,
@@ -134,7 +144,7 @@ OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
        "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "trace_lights", "trace_mesh",
-       "trace_mesh_uv", "env_sample",
+       "trace_mesh_uv", "mesh_build", "env_sample",
        "trace_lights_env", "trace_glass_env", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
        "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
