@@ -44,6 +44,8 @@
  *                       <- no counterpart (raytrace_scene adds nothing on a miss, base.py:100-121): an
  *                          equirectangular environment map that every ray which meets no shape samples
  *   rtx_mesh_build      <- no counterpart: the table of rtx_trace_mesh (rows, tree, boxes) made on the device
+ *   rtx_mesh_aovs       <- no counterpart: rtx_primary_aovs' passes for a scene with triangle meshes, with
+ *                          the triangle's number, barycentrics and face normal
  *
  * Conventions
  *  - All array pointers are DEVICE pointers (hipMalloc / torch caching allocator), read-only
@@ -888,6 +890,62 @@ int rtx_mesh_build(const double* vertices, int64_t n_vertices, const int32_t* fa
                    int64_t n_triangles, const double* normals, const int32_t* mesh_smooth, const double* uvs,
                    const double* header, double* table, int64_t table_words, int max_leaf, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* Primary-hit render passes of a mesh scene (HipRenderer.render_mesh_aovs / trace_mesh_aovs; DESIGN.md §20;
+ * rtx_primary_aovs sees spheres alone): intermediates of rtx_trace_mesh's level-0 hit for n explicit rays
+ * (the layout of rtx_trace_rays, origin_stride 0 or n) through the spheres of `scene` (n_spheres may be 0)
+ * and the triangle group of `mesh`, written out instead of shaded. Everything is float64 in the operation
+ * order rtx_trace_mesh fixes above: the sphere test, the triangle test, P = O + D*t, a sphere's normal
+ * (P - C) * (1 / radius), a triangle's N_g, interpolated N and their flips.
+ * tmin is the spheres' nearest distance (base.py:98), tt the group's hit (smallest t, lowest RTX_T_NUM among
+ * equal t); the ray's nearest is min(tmin, tt). The FIRST HIT is the first sphere in scene order at the
+ * nearest distance if there is one, else the triangle: the hit rtx_trace_mesh shades first.
+ *   depth            double [n]     the nearest distance; exactly FARAWAY (1e39) on a miss
+ *   id               int32  [n]     the first hit's shape: shape_ids[s] for sphere s, shape_ids[n_spheres + mesh]
+ *                                   for a triangle of mesh `mesh` (RTX_T_MESH); -1 on a miss
+ *   hits             int32  [n]     the spheres at the nearest distance, plus 1 if the group's t equals it;
+ *                                   0 on a miss
+ *   position         double [3][n]  P = O + D * nearest
+ *   normal           double [3][n]  the shading normal N of the first hit: the sphere's, or the triangle's (a flat
+ *                                   row: N_g flipped to oppose the ray; a row with vertex normals: the normalised
+ *                                   interpolation, flipped to N_g's side)
+ *   geometric_normal double [3][n]  a triangle's N_g flipped to oppose the ray; a sphere's normal. position +
+ *                                   geometric_normal * 0.0001 is the kernel's nudged point Q (shader.py:77)
+ *   albedo           double [3][n]  the texture's colour at the first hit: the constant, the checker cell as
+ *                                   1.0 / 0.0, a sphere's image texel (the blob's), a UV-mapped mesh's image
+ *                                   colour (the lookup of rtx_trace_mesh_uv above; black for a table without a
+ *                                   UV part)
+ *   lit              uint8  [n]     bit i: row i of `lights` reaches the first hit under rtx_trace_mesh's shadow
+ *                                   rule (along L from Q, nothing strictly nearer than a sphere's own distance;
+ *                                   t_self = FARAWAY on a triangle). n_lights <= 8 rows fit the byte; with the
+ *                                   one-row table it is 0 / 1 as rtx_primary_aovs' lit
+ *   triangle         int32  [n]     the first hit's RTX_T_NUM when it is a triangle; -1 on a sphere or a miss
+ *   bary             double [2][n]  (u, v) of that triangle's test, computed again from its row (the same bits
+ *                                   as the walk's); 0 on a sphere or a miss
+ * On a miss every per-hit pass is 0 and triangle is -1. The passes stop at level 0. Every output pointer may
+ * be NULL: that pass is neither computed nor stored; without lit there is no shadow walk, without albedo no
+ * texel lookup, without any per-hit pass no hit point. The RTX_MESH_AOV_* bits name the passes for the layers
+ * above (rt::mesh_aovs's `passes` mask; results in bit order).
+ * shape_ids, int32 [n_spheres + the table's RTX_MH_NMESH] on the device or NULL: what id reports, the
+ * spheres' first, then the meshes' in table order (HipRenderer passes each shape's index in scene.shapes);
+ * NULL is the identity, s and n_spheres + mesh. Read per lane once, at the hit.
+ * A blob whose magic or sphere count disagrees with n_spheres means no spheres, a mesh header that does not
+ * fit mesh_words no triangles, as in rtx_trace_mesh. Needs no workspace and has no status word; asynchronous
+ * on `stream`, never allocates, never synchronises.
+ * RTX_E_ARG (before any HIP call) for a null scene, mesh, lights, origins or dirs, all ten output pointers
+ * null, n_spheres outside 0..RTX_MAX_SPHERES, mesh_words outside RTX_MESH_HDR_WORDS..2^31 - 1, n_lights
+ * outside 1..RTX_MAX_POINT_LIGHTS, a negative n, or an origin_stride other than 0 or n; zero rays return
+ * RTX_OK without a launch. */
+enum {
+  RTX_MESH_AOV_DEPTH = 1, RTX_MESH_AOV_ID = 2, RTX_MESH_AOV_HITS = 4, RTX_MESH_AOV_POSITION = 8,
+  RTX_MESH_AOV_NORMAL = 16, RTX_MESH_AOV_GEOMETRIC_NORMAL = 32, RTX_MESH_AOV_ALBEDO = 64, RTX_MESH_AOV_LIT = 128,
+  RTX_MESH_AOV_TRIANGLE = 256, RTX_MESH_AOV_BARY = 512, RTX_MESH_AOV_ALL = 1023
+};
+int rtx_mesh_aovs(const double* scene, int n_spheres, const double* mesh, int64_t mesh_words, const double* lights,
+                  int n_lights, const int32_t* shape_ids, const double* origins, int64_t origin_stride,
+                  const double* dirs, int64_t n, double* depth, int32_t* id, int32_t* hits, double* position,
+                  double* normal, double* geometric_normal, double* albedo, uint8_t* lit, int32_t* triangle,
+                  double* bary, void* stream);
 
 /* Frame assembly of the multi-GPU path (render_image_pipeline's row-tile gather, SURVEY.md §8e;
  * the reference renders one process-local frame, application.py:43-52): `tiles` holds n_parts

@@ -25,6 +25,8 @@
 //                        through the spheres and the triangles of a mesh table (rtx_trace_mesh)
 //   rt::mesh_build    <- no counterpart: the table of rt::trace_mesh made on the device from the meshes' arrays
 //                        (rtx_mesh_build), value for value the host's meshes.mesh_table
+//   rt::mesh_aovs     <- no counterpart: rt::primary_aovs_rays' passes for a scene with a mesh table, with the
+//                        triangle's number, barycentrics and face normal (rtx_mesh_aovs)
 //   rt::trace_mesh_uv <- no counterpart: rt::trace_mesh on a table with texture coordinates and texel blocks
 //                        (rtx_trace_mesh_uv): image textures on meshes
 //   rt::env_sample, rt::trace_lights_env, rt::trace_glass_env
@@ -982,6 +984,81 @@ at::Tensor trace_mesh_uv(const at::Tensor& scene, int64_t n_spheres, const at::T
   return trace_mesh_call(scene, n_spheres, mesh, lights, origins, dirs, max_bounces, out_kind, check, true);
 }
 
+// ---- primary-hit render passes of a mesh scene (rtx_mesh_aovs) ------------------------------------------
+// `passes`: a mask of RTX_MESH_AOV_* bits; the result holds one tensor per set bit, in bit order: depth float64
+// [n], id / hits int32 [n], position / normal / geometric_normal / albedo float64 [3, n], lit uint8 [n], triangle
+// int32 [n], bary float64 [2, n]. Shared by the kernel and its Meta form.
+std::vector<at::Tensor> new_mesh_aovs(const at::Tensor& like, int64_t n, int64_t passes) {
+  TORCH_CHECK(passes > 0 && (passes & ~(int64_t)RTX_MESH_AOV_ALL) == 0,
+              "passes must be a non-empty mask of RTX_MESH_AOV_* bits (1..", (int)RTX_MESH_AOV_ALL, "), got ", passes);
+  const auto o = like.options();
+  std::vector<at::Tensor> out;
+  if (passes & RTX_MESH_AOV_DEPTH) out.push_back(at::empty({n}, o.dtype(at::kDouble)));
+  if (passes & RTX_MESH_AOV_ID) out.push_back(at::empty({n}, o.dtype(at::kInt)));
+  if (passes & RTX_MESH_AOV_HITS) out.push_back(at::empty({n}, o.dtype(at::kInt)));
+  if (passes & RTX_MESH_AOV_POSITION) out.push_back(at::empty({3, n}, o.dtype(at::kDouble)));
+  if (passes & RTX_MESH_AOV_NORMAL) out.push_back(at::empty({3, n}, o.dtype(at::kDouble)));
+  if (passes & RTX_MESH_AOV_GEOMETRIC_NORMAL) out.push_back(at::empty({3, n}, o.dtype(at::kDouble)));
+  if (passes & RTX_MESH_AOV_ALBEDO) out.push_back(at::empty({3, n}, o.dtype(at::kDouble)));
+  if (passes & RTX_MESH_AOV_LIT) out.push_back(at::empty({n}, o.dtype(at::kByte)));
+  if (passes & RTX_MESH_AOV_TRIANGLE) out.push_back(at::empty({n}, o.dtype(at::kInt)));
+  if (passes & RTX_MESH_AOV_BARY) out.push_back(at::empty({2, n}, o.dtype(at::kDouble)));
+  return out;
+}
+
+// Shapes and ranges of rt::mesh_aovs' arguments (check_mesh's, without a bounce cap or an out_kind): returns n.
+// shape_ids, if given: int32 [n_spheres + meshes], at least one mesh.
+int64_t check_mesh_aovs(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh, const at::Tensor& lights,
+                        const std::optional<at::Tensor>& shape_ids, const at::Tensor& origins,
+                        const at::Tensor& dirs) {
+  const int64_t n = check_mesh(scene, n_spheres, mesh, lights, origins, dirs, 0, RTX_OUT_F64_SOA);
+  if (shape_ids.has_value())
+    TORCH_CHECK(shape_ids->scalar_type() == at::kInt && shape_ids->dim() == 1 && shape_ids->numel() >= n_spheres + 1,
+                "shape_ids must be ", at::kInt, " [n_spheres + meshes] (one entry per sphere, then one per mesh of "
+                "the table), got ", shape_ids->scalar_type(), " ", shape_ids->sizes());
+  return n;
+}
+
+std::vector<at::Tensor> mesh_aovs(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh,
+                                  const at::Tensor& lights, const std::optional<at::Tensor>& shape_ids,
+                                  const at::Tensor& origins, const at::Tensor& dirs, int64_t passes, bool check) {
+  check_gpu(scene, "scene", at::kDouble);
+  const at::OptionalDeviceGuard guard(at::device_of(scene));
+  for (const NamedTensor& a : {NamedTensor{mesh, "mesh"}, NamedTensor{lights, "lights"},
+                               NamedTensor{origins, "origins"}, NamedTensor{dirs, "dirs"}}) {
+    check_gpu(a.t, a.name, at::kDouble);
+    check_same_device(scene, a.t, a.name);
+  }
+  if (shape_ids.has_value()) {
+    check_gpu(*shape_ids, "shape_ids", at::kInt);
+    check_same_device(scene, *shape_ids, "shape_ids");
+  }
+  const int64_t n = check_mesh_aovs(scene, n_spheres, mesh, lights, shape_ids, origins, dirs);
+  std::vector<at::Tensor> out = new_mesh_aovs(scene, n, passes);
+  if (check) {
+    check_headers(scene, n_spheres);
+    check_mesh_header(mesh);
+    if (shape_ids.has_value()) {  // (one more synchronous copy of the header's mesh count)
+      const double meshes = mesh.narrow(0, RTX_MH_NMESH, 1).item<double>();
+      TORCH_CHECK((double)shape_ids->numel() == (double)n_spheres + meshes, "shape_ids must have one entry per sphere "
+                  "and per mesh of the table (", n_spheres, " + ", meshes, "), got ", shape_ids->sizes());
+    }
+  }
+  if (n == 0) return out;  // (an empty tensor's pointer may be null)
+  void* p[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t k = 0;
+  for (int b = 0; b < 10; ++b)
+    if (passes & (int64_t(1) << b)) p[b] = out[k++].data_ptr();
+  check_rc(rtx_mesh_aovs(scene.data_ptr<double>(), (int)n_spheres, mesh.data_ptr<double>(), mesh.numel(),
+                         lights.data_ptr<double>(), (int)lights.size(0),
+                         shape_ids.has_value() ? shape_ids->data_ptr<int32_t>() : nullptr, origins.data_ptr<double>(),
+                         origins.dim() == 1 ? 0 : n, dirs.data_ptr<double>(), n, (double*)p[0], (int32_t*)p[1],
+                         (int32_t*)p[2], (double*)p[3], (double*)p[4], (double*)p[5], (double*)p[6], (uint8_t*)p[7],
+                         (int32_t*)p[8], (double*)p[9], stream_of(scene)),
+           "rtx_mesh_aovs");
+  return out;
+}
+
 at::Tensor trace_lights_env(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& lights,
                             const at::Tensor& origins, const at::Tensor& dirs, int64_t max_bounces, int64_t out_kind,
                             const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, bool check) {
@@ -1197,6 +1274,12 @@ at::Tensor trace_mesh_meta(const at::Tensor& scene, int64_t n_spheres, const at:
                     out_kind);
 }
 
+std::vector<at::Tensor> mesh_aovs_meta(const at::Tensor& scene, int64_t n_spheres, const at::Tensor& mesh,
+                                       const at::Tensor& lights, const std::optional<at::Tensor>& shape_ids,
+                                       const at::Tensor& origins, const at::Tensor& dirs, int64_t passes, bool) {
+  return new_mesh_aovs(scene, check_mesh_aovs(scene, n_spheres, mesh, lights, shape_ids, origins, dirs), passes);
+}
+
 at::Tensor env_sample_meta(const at::Tensor& texels, c10::ArrayRef<double> gain, double turn, const at::Tensor& dirs) {
   rtx_env_t env;
   check_env(texels, gain, turn, env);
@@ -1380,6 +1463,8 @@ TORCH_LIBRARY(rt, m) {
         "int max_bounces, int out_kind, bool check=True) -> Tensor");
   m.def("trace_mesh_uv(Tensor scene, int n_spheres, Tensor mesh, Tensor lights, Tensor origins, Tensor dirs, "
         "int max_bounces, int out_kind, bool check=True) -> Tensor");
+  m.def("mesh_aovs(Tensor scene, int n_spheres, Tensor mesh, Tensor lights, Tensor? shape_ids, Tensor origins, "
+        "Tensor dirs, int passes, bool check=True) -> Tensor[]");
   m.def("mesh_build(Tensor vertices, Tensor faces, Tensor tri_mesh, Tensor? normals, Tensor? mesh_smooth, Tensor? uvs, "
         "Tensor(a!) skeleton, int max_leaf, Tensor(b!) workspace, bool check=True) -> Tensor");
   m.def("env_sample(Tensor texels, float[] gain, float turn, Tensor dirs) -> Tensor");
@@ -1425,6 +1510,7 @@ TORCH_LIBRARY_IMPL(rt, CUDA, m) {
   m.impl("trace_mesh", &trace_mesh);
   m.impl("trace_mesh_uv", &trace_mesh_uv);
   m.impl("mesh_build", &mesh_build);
+  m.impl("mesh_aovs", &mesh_aovs);
   m.impl("env_sample", &env_sample);
   m.impl("trace_lights_env", &trace_lights_env);
   m.impl("trace_glass_env", &trace_glass_env);
@@ -1454,6 +1540,7 @@ TORCH_LIBRARY_IMPL(rt, CPU, m) {
   m.impl("trace_mesh", &trace_mesh);
   m.impl("trace_mesh_uv", &trace_mesh_uv);
   m.impl("mesh_build", &mesh_build);
+  m.impl("mesh_aovs", &mesh_aovs);
   m.impl("env_sample", &env_sample);
   m.impl("trace_lights_env", &trace_lights_env);
   m.impl("trace_glass_env", &trace_glass_env);
@@ -1481,6 +1568,7 @@ TORCH_LIBRARY_IMPL(rt, Meta, m) {
   m.impl("trace_mesh", &trace_mesh_meta);
   m.impl("trace_mesh_uv", &trace_mesh_meta);
   m.impl("mesh_build", &mesh_build_meta);
+  m.impl("mesh_aovs", &mesh_aovs_meta);
   m.impl("env_sample", &env_sample_meta);
   m.impl("trace_lights_env", &trace_lights_env_meta);
   m.impl("trace_glass_env", &trace_glass_env_meta);

@@ -16,6 +16,7 @@ from .base import (
     HipRGBColor,
     HipVector3D,
     HipVectorArray3D,
+    MESH_AOV_NAMES,
     OCC_NAMES,
 )
 from .shader import HipShader, ImageTexture, Texture, TextureChecker
@@ -33,6 +34,7 @@ __all__ = [
     "ImageTexture",
     "HipVector3D",
     "HipVectorArray3D",
+    "MESH_AOV_NAMES",
     "OCC_NAMES",
     "Texture",
     "TextureChecker",

@@ -134,6 +134,7 @@ EXPORTS = (
     "rtx_mesh_build_nodes",
     "rtx_mesh_build_workspace_bytes",
     "rtx_mesh_build",
+    "rtx_mesh_aovs",
 )
 
 # RTX_AOV_*: the primary-hit passes (rtx_primary_aovs; rt::primary_aovs's mask), in result order
@@ -141,6 +142,10 @@ AOV_DEPTH, AOV_ID, AOV_HITS, AOV_POSITION, AOV_NORMAL, AOV_ALBEDO, AOV_LIT = 1, 
 AOV_ALL = 127
 AOV_PASSES = {"depth": AOV_DEPTH, "id": AOV_ID, "hits": AOV_HITS, "position": AOV_POSITION,
               "normal": AOV_NORMAL, "albedo": AOV_ALBEDO, "lit": AOV_LIT}
+# RTX_MESH_AOV_*: the primary-hit passes of a mesh scene (rtx_mesh_aovs; rt::mesh_aovs's mask), in result order
+MESH_AOV_PASSES = {name: 1 << b for b, name in enumerate(
+    ("depth", "id", "hits", "position", "normal", "geometric_normal", "albedo", "lit", "triangle", "bary"))}
+MESH_AOV_ALL = 1023
 # RTX_OCC_*: the occlusion passes (rtx_occlusion; rt::occlusion's mask), in result order
 OCC_AO, OCC_SOFT = 1, 2
 OCC_ALL = 3
@@ -242,6 +247,8 @@ _SIGS = {
     "rtx_mesh_build_workspace_bytes": (_size, [_i64, _i64]),
     "rtx_mesh_build": (_i32, [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                               _c_void_p, _i64, _i32, _c_void_p, _size, _c_void_p]),
+    "rtx_mesh_aovs": (_i32, [_c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p, _c_void_p, _i64, _c_void_p,
+                             _i64] + [_c_void_p] * 11),
 }
 
 _lib = None

@@ -41,6 +41,39 @@ def is_mesh_scene(shapes) -> bool:
     return any(isinstance(sh, TriangleMesh) for sh in shapes)
 
 
+def shape_ids(shapes) -> np.ndarray:
+    """What rtx_mesh_aovs' ``id`` pass reports (its ``shape_ids``), int32: the indices in ``shapes`` of the
+    shapes that are no ``TriangleMesh`` (the spheres, in the packer's order), then those of the meshes (in
+    the table's order)."""
+    meshes = [i for i, sh in enumerate(shapes) if isinstance(sh, TriangleMesh)]
+    others = [i for i, sh in enumerate(shapes) if not isinstance(sh, TriangleMesh)]
+    return np.asarray(others + meshes, dtype=np.int32)
+
+
+def triangle_faces(shapes, numbers) -> tuple:
+    """(shape_index, face_index), int64 arrays shaped like ``numbers``: for every triangle number of the
+    scene's group (the ``triangle`` pass of render_mesh_aovs: scene order, then face order) the index in
+    ``shapes`` of the mesh that owns it and the face's index in that mesh's ``faces``; -1 and -1 where the
+    number is -1. ValueError for a number outside -1..T - 1."""
+    num = np.asarray(numbers)
+    if not np.issubdtype(num.dtype, np.integer):
+        raise ValueError(f"triangle_faces: numbers must be integers, got {num.dtype}")
+    num = num.astype(np.int64)
+    where = [i for i, sh in enumerate(shapes) if isinstance(sh, TriangleMesh)]
+    ends = np.cumsum([len(shapes[i].faces) for i in where], dtype=np.int64)  # the first number after each mesh
+    total = int(ends[-1]) if len(where) else 0
+    if num.size and (num.min() < -1 or num.max() >= total):
+        raise ValueError(f"triangle_faces: a number lies outside -1..{total - 1} (the scene has {total} triangles)")
+    hit = num >= 0
+    mesh = np.searchsorted(ends, np.where(hit, num, 0), side="right")
+    starts = np.concatenate([[0], ends[:-1]]).astype(np.int64) if len(where) else np.zeros(0, dtype=np.int64)
+    if not len(where):
+        return np.full(num.shape, -1, dtype=np.int64), np.full(num.shape, -1, dtype=np.int64)
+    shape_index = np.where(hit, np.asarray(where, dtype=np.int64)[mesh], -1)
+    face_index = np.where(hit, num - starts[mesh], -1)
+    return shape_index, face_index
+
+
 def check_bounces(max_bounces) -> int:
     """The bounce cap of a mesh render: an int in 0..MAX_BOUNCES. ValueError for None (the kernel keeps
     a lane's pending rays in a stack sized by the cap) and for a larger cap."""

@@ -77,6 +77,17 @@ that device's current HIP stream and returns a new tensor):
   ``rt::trace_mesh`` on a table with texture coordinates and texel blocks (rtx_trace_mesh_uv; DESIGN.md §18):
   the table ``meshes.mesh_table`` builds when a mesh has an ``ImageTexture``. With ``check=True`` the offsets
   of the two new parts are checked against the table's length as well.
+* ``rt::mesh_aovs(scene, n_spheres, mesh, lights, shape_ids, origins, dirs, passes, check=True)`` — the
+  primary-hit render passes of a mesh scene for explicit rays (rtx_mesh_aovs; HipRenderer.render_mesh_aovs /
+  trace_mesh_aovs; contract in include/rtx_hip.h): ``scene``, ``mesh``, ``lights``, origins and
+  dirs as ``rt::trace_mesh`` takes them (a table with a UV part too), ``shape_ids`` int32 [n_spheres + meshes] or
+  None (what ``id`` reports per sphere, then per mesh; None: the position in that order). ``passes`` is a mask of
+  the RTX_MESH_AOV_* bits (``_lib.MESH_AOV_PASSES``): 1 depth float64 [n], 2 id, 4 hits int32 [n], 8 position,
+  16 normal, 32 geometric_normal, 64 albedo float64 [3, n], 128 lit uint8 [n] (bit i: lights row i), 256 triangle
+  int32 [n], 512 bary float64 [2, n]; the result is a list with one tensor per set bit, in bit order. A pass
+  that is not requested is neither computed nor stored. With ``check=True`` the headers of the blob and of the
+  mesh table are read back and ``shape_ids``' length is checked against the table's mesh count. Needs no
+  workspace.
 * ``rt::mesh_build(vertices, faces, tri_mesh, normals, mesh_smooth, uvs, skeleton, max_leaf, workspace,
   check=True)`` — the table of ``rt::trace_mesh`` / ``rt::trace_mesh_uv`` made on the device (rtx_mesh_build;
   contract in include/rtx_hip.h): the device arrays of ``meshes.device_inputs`` (float64 [V, 3],
@@ -144,7 +155,7 @@ OPS_LIB = Path(__file__).resolve().parent / "librt_ops.so"
 RTX_LIB = Path(__file__).resolve().parent / "librtx_hip.so"  # what librt_ops.so links by $ORIGIN
 OPS = ("render_tile", "render_frames", "trace", "shade_hits", "intersect", "quantize_u8", "assemble_rows",
        "resolve_samples", "primary_aovs", "primary_aovs_rays", "occlusion", "trace_glass", "trace_lights", "trace_mesh",
-       "trace_mesh_uv", "mesh_build", "env_sample",
+       "trace_mesh_uv", "mesh_build", "mesh_aovs", "env_sample",
        "trace_lights_env", "trace_glass_env", "edge_mask", "sample_dirs", "resolve_scatter", "camera_rays",
        "status", "workspace_bytes",
        # the row-tiled multi-GPU frame (rtx_tiles_*: render, RCCL gather, assembly in one native call)
